@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- fp64 CSR SpMV (y = alpha*A*x + beta*y, alpha = beta = 1) on MI355X through the C ABI.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up (W SpMVs; the first builds and settles the plan), times ONE region of exactly K steps and prints the line.
+`--full` adds everything else below: the repeated regions, the per-launch / kernel-clock / cold protocols, the copy ceiling, the launch
+floor, the sensitivity variant, the extra legs, the CPU baseline and, for N > 1, the pipelined dependent step and the side legs.
+`--dump-outputs DIR` writes, after the timed steps, the y of the last timed step as DIR/y.npy (float64; a fixed seeded sample of at most
+DUMP_MAX_ROWS rows when y is longer, see dump_rows); the inputs are seeded, so two builds can be compared output for output.
 
 A "step" is one SpMV over one synthetic matrix resident in HBM.  N = 1 runs BASELINE.json configs[1]
 (Hardesty3-sized stand-in, 8,217,820 x 7,591,564, 40,451,632 nnz, adaptive strategy).  N > 1: one rank per GPU
@@ -13,18 +19,18 @@ the GPU -- the parent imports neither torch nor the library), relays rank 0's li
 Rank 0 prints ONE JSON line.
 
 value       = 2 * nnz_total * K / wall_seconds / 1e9  [GFLOP/s], wall-clock over exactly K back-to-back steps bracketed by
-              barrier + torch.cuda.synchronize() on both sides, max over ranks; the region is repeated REGION_REPS times inside the one
-              command and wall_seconds is the MEDIAN repetition (the reference reports medians, benchmark_time.cpp:23-43); the
-              event time of the same regions stands beside it (ms_per_step_events).
+              barrier + torch.cuda.synchronize() on both sides, max over ranks; under --full the region is repeated REGION_REPS times
+              inside the one command and wall_seconds is the MEDIAN repetition (the reference reports medians, benchmark_time.cpp:23-43);
+              the event time of the same regions stands beside it (ms_per_step_events).
 roofline    = algorithmic bytes (12*nnz + 4*(m+1) + 8*n + 16*m) / the dominant kernel's average launch duration over the
               TIMED REGION (hipEvents on the library stream around the K launches, median repetition): the figure the committed rocprofv3
               --kernel-trace --stats summary of the same command averages to.  Beside it: `per_launch_protocol` -- the REFERENCE HARNESS'S
               protocol (benchmark/csr_spmv.hpp:66-74: y reset by a device copy before every launch, one event pair per launch, median;
               it also holds the protocol's floor of marker packets + dispatch latency), the figure every sweep gate is counted on -- and
               `kernel_clock_reset_protocol`: the kernel's own start / stop events (spmv_acc_time_spmv_kernels) under that protocol.
-cpu_baseline= the oracle (CPU restatement of cli/verification.cpp:56-66) on the host cores, same matrix.
+cpu_baseline= the oracle (CPU restatement of cli/verification.cpp:56-66) on the host cores, same matrix (--full; null otherwise).
 
-N = 1, default: the extra legs (configs[2] sweep, configs[3] R-MAT 25, configs[4] banded shard) are measured in one CHILD process per matrix, as the
+N = 1, --full: the extra legs (configs[2] sweep, configs[3] R-MAT 25, configs[4] banded shard) are measured in one CHILD process per matrix, as the
 reference's batch runs its CLI once per matrix file (examples/large-data-set-batch.sh); `--legs-in-process` keeps them here.
 """
 import argparse
@@ -67,13 +73,16 @@ def roofline_block(b_alg, b2b_ms, kernel_ms, ev_ms, cold=None):
     fr = lambda ms: round(b_alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)  # noqa: E731
     out = {"bound": "hbm", "achieved": gbs(b2b_ms), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs(b2b_ms) / HBM_PEAK_GBS, 4),
            "definition": dict(ROOFLINE_DEFINITION),
-           "kernel_clock_reset_protocol": {"what": "the kernel's own start / stop events (hipExtLaunchKernelGGL), y reset by a device copy before each launch, median",
-                                           "launch_ms_median": round(kernel_ms, 6), "achieved": gbs(kernel_ms), "frac": fr(kernel_ms)},
-           "per_launch_protocol": {"what": "event pair around each call, y reset before it, median (benchmark/csr_spmv.hpp:66-74): kernel + the protocol's floor",
-                                   "launch_ms_median": round(ev_ms, 6), "achieved": gbs(ev_ms), "frac": fr(ev_ms)},
            "algorithmic_bytes_per_launch": b_alg, "launch_ms_mean": round(b2b_ms, 6),
            "back_to_back": {"launch_ms_mean": round(b2b_ms, 6), "achieved": gbs(b2b_ms), "frac": fr(b2b_ms)}}
-    if cold is not None:
+    # (a plain run measures the timed region only: the two per-launch clocks are None there and their objects are left out)
+    if kernel_ms is not None:
+        out["kernel_clock_reset_protocol"] = {"what": "the kernel's own start / stop events (hipExtLaunchKernelGGL), y reset by a device copy before each launch, median",
+                                              "launch_ms_median": round(kernel_ms, 6), "achieved": gbs(kernel_ms), "frac": fr(kernel_ms)}
+    if ev_ms is not None:
+        out["per_launch_protocol"] = {"what": "event pair around each call, y reset before it, median (benchmark/csr_spmv.hpp:66-74): kernel + the protocol's floor",
+                                      "launch_ms_median": round(ev_ms, 6), "achieved": gbs(ev_ms), "frac": fr(ev_ms)}
+    if cold is not None and ev_ms is not None:
         out["cold_protocol"] = {"what": f"per-launch protocol with {FLUSH_BYTES >> 20} MiB of default-policy scratch traffic before every timed launch: nothing of the "
                                         "matrix in the L2s or the Infinity Cache when it starts (context, never a gate)",
                                 "launch_ms_median": round(cold, 6), "achieved": gbs(cold), "frac": fr(cold)}
@@ -126,6 +135,27 @@ def median_region(run, reps, sync_all, reduce_max=None):
     return float(np.median(walls)), [float(w) for w in walls]
 
 
+DUMP_MAX_ROWS = 1 << 22  # --dump-outputs: 32 MiB of float64 at most
+DUMP_SEED = 0x5EED
+
+
+def dump_rows(m):
+    """The rows of y that --dump-outputs writes: all of them up to DUMP_MAX_ROWS, else a fixed seeded sample of DUMP_MAX_ROWS rows in ascending
+    order (the same rows for the same length, whatever the build)."""
+    if m <= DUMP_MAX_ROWS:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=DUMP_MAX_ROWS, replace=False))
+
+
+def dump_outputs(torch, out_dir, y):
+    """Write the timed path's result vector as out_dir/y.npy (float64)."""
+    rows = dump_rows(y.numel())
+    if rows is not None:
+        y = y.index_select(0, torch.from_numpy(rows).to(y.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), y.detach().to(torch.float64).cpu().numpy())
+
+
 def budget_left(budget_s):
     """Seconds left of this process's wall-clock allowance (N > 1: SPMV_ACC_BENCH_BUDGET_S, default 420 -- the side legs of a multi-GPU run
     are skipped rather than allowed to eat the driver's timeout when an exchange turns out slow)."""
@@ -141,6 +171,11 @@ def parse():
                    help="hardesty3 | banded | rmat | one of the large-set names (boneS10, Bump_2911, ...)")
     p.add_argument("--strategy", default=None, help="KERNEL_STRATEGY name (default: adaptive; banded/rmat per BASELINE)")
     p.add_argument("--scale", type=float, default=1.0, help="shrink the workload (for rehearsals only)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: repeated regions, the other timing protocols, copy ceiling, launch floor, "
+                        "sensitivity, the extra legs, the CPU baseline (N > 1: the pipelined dependent step and the side legs)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the y of the last timed step as DIR/y.npy (float64, seeded sample of long vectors)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-sensitivity", action="store_true", help="skip the far_fraction=0 variant of the N=1 workload")
     p.add_argument("--no-legs", action="store_true",
@@ -617,7 +652,8 @@ def extra_legs(torch, device, headline, in_process=False):
     return out
 
 
-def sharded_leg(torch, dist, args, W, x, y0, alpha, beta, rank, world, device, backend, force_dist, steps, warmup, bounds=None, time_left=None):
+def sharded_leg(torch, dist, args, W, x, y0, alpha, beta, rank, world, device, backend, force_dist, steps, warmup, bounds=None, time_left=None,
+                dump_dir=None):
     """N > 1: one RowShardedSpmv over this rank's shard -- local SpMV on the engine's own stream, ONE exchange of the y slices
     per step (RCCL allgather or the point-to-point fan-out, whichever the timing on this communicator prefers).  Returns the
     max-over-ranks wall time of `steps` steps (barrier + synchronize on both sides) and the SpMV-only launch time."""
@@ -660,11 +696,16 @@ def sharded_leg(torch, dist, args, W, x, y0, alpha, beta, rank, world, device, b
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t.tolist()
 
-    # the K-step region `reps` times (each bracketed by barrier + synchronize, MAX over ranks per repetition), median; a first repetition that
-    # already takes long (a slow exchange) is not repeated as often: the run must end inside the driver's timeout
-    wall1, _ = median_region(region, 1, sync_all, max_over_ranks)
-    reps = REGION_REPS if wall1 * REGION_REPS < 30.0 else 3
+    # --full: the K-step region `reps` times (each bracketed by barrier + synchronize, MAX over ranks per repetition), median; a first repetition
+    # that already takes long (a slow exchange) is not repeated as often: the run must end inside the driver's timeout.  A plain run: one region.
+    if args.full:
+        wall1, _ = median_region(region, 1, sync_all, max_over_ranks)
+        reps = REGION_REPS if wall1 * REGION_REPS < 30.0 else 3
+    else:
+        reps = 1
     wall, walls = median_region(region, reps, sync_all, max_over_ranks)
+    if dump_dir and rank == 0:
+        dump_outputs(torch, dump_dir, eng.gathered())
     extra["region_reps"] = reps
     extra["ms_per_step_wall_all"] = [round(w / steps * 1e3, 6) for w in walls]
     # SpMV-only (no exchange) for the same shard, per-launch hipEvents
@@ -682,7 +723,7 @@ def sharded_leg(torch, dist, args, W, x, y0, alpha, beta, rank, world, device, b
     # into C chunks and sending chunk c while chunk c+1 computes (RowShardedSpmv.step(pipeline=C)).  Timed with every step
     # waiting for its exchange; C = 1 is the serial kernel + exchange.
     # (a collective decision: `time_left()` is the MINIMUM over ranks of what is left of the run's allowance -- every rank skips or none does)
-    if backend == "nccl" and (time_left is None or time_left() > 60.0):
+    if args.full and backend == "nccl" and (time_left is None or time_left() > 60.0):
         try:
             dep = eng.tune_pipeline(alpha, beta, x, candidates=(1, 2, 4, 8), warm=2, iters=max(3, min(steps, 10)))
             extra["dependent_step_ms_by_pipeline"] = {str(k): round(v, 6) for k, v in dep.items()}
@@ -1006,38 +1047,48 @@ def main():
                 out_extra["first_call_ms"] = round((time.perf_counter() - tf) * 1e3, 3)
                 out_extra["first_call_host_prepare_ms"] = round(spmv_acc_amd.load_library().spmv_acc_last_prepare_us() * 1e-3, 3)
                 out_extra["settle_rest_ms"] = round(spmv_acc_amd.prepare(m, n, nnz, W["rp"], W["ci"], W["v"], x, strategy=strat, beta=beta), 3)
+        if not args.full:
+            # (one launch through the timing entry, so that it makes its event pair here and not inside the timed wall clock)
+            spmv_acc_amd.time_spmv_region(strat, 1, alpha, beta, m, n, nnz, W["rp"], W["ci"], W["v"], x, y)()
         torch.cuda.synchronize()
         y.copy_(y0)
         # timed region: exactly K back-to-back launches between one hipEvent pair on the library stream and nothing else (the plan is settled,
-        # the events exist, arguments are converted once: spmv_acc_time_spmv_region); one untimed region first, then REGION_REPS timed ones
+        # the events exist, arguments are converted once: spmv_acc_time_spmv_region).  A plain run times ONE region; --full runs one untimed
+        # region first, then REGION_REPS timed ones.
         region = spmv_acc_amd.time_spmv_region(strat, args.steps, alpha, beta, m, n, nnz, W["rp"], W["ci"], W["v"], x, y)
-        region()
+        reps = REGION_REPS if args.full else 1
+        if args.full:
+            region()
         region_event_ms = []
-        wall, walls = median_region(lambda: region_event_ms.append(region()), REGION_REPS, sync_all)
+        wall, walls = median_region(lambda: region_event_ms.append(region()), reps, sync_all)
+        if args.dump_outputs:
+            dump_outputs(torch, args.dump_outputs, y)
         b2b_ms = float(np.median(region_event_ms)) / args.steps
-        out_extra["region_reps"] = REGION_REPS
+        out_extra["region_reps"] = reps
         out_extra["ms_per_step_events"] = round(b2b_ms, 6)
         out_extra["ms_per_step_wall_all"] = [round(w / args.steps * 1e3, 6) for w in walls]
         out_extra["ms_per_step_events_all"] = [round(e / args.steps, 6) for e in region_event_ms]
-        # the reference harness's protocol (csr_spmv.hpp:66-74): y reset by a device copy before every launch, one event pair
-        # per launch, median -- roofline.per_launch_protocol (rounds 1-4 quoted roofline.frac on it; since round 5 roofline.frac is the timed
-        # region's back-to-back figure: ROOFLINE_DEFINITION above, frozen)
-        ms = spmv_acc_amd.time_spmv(strat, max(20, min(args.steps, 50)), alpha, beta, m, n, nnz, W["rp"], W["ci"], W["v"], x, y, y0=y0)
-        ev_ms = float(np.median(ms))
-        # the same protocol with the library's kernel clock on: each launch's own start / stop timestamps
-        ev2, kn_ms, kn_launches = spmv_acc_amd.time_spmv_kernels(strat, max(20, min(args.steps, 50)), alpha, beta, m, n, nnz, W["rp"], W["ci"], W["v"], x, y, y0=y0)
-        kernel_ms = float(np.median(kn_ms))
-        out_extra["kernel_clock_ms_median"] = round(kernel_ms, 6)
-        out_extra["kernel_clock_launches_per_step"] = int(np.median(kn_launches))
-        out_extra["per_launch_reset_ms_median_under_kernel_clock"] = round(float(np.median(ev2)), 6)
-        out_extra["per_launch_reset_ms_median"] = round(ev_ms, 6)
-        out_extra["per_launch_reset_ms_min"] = round(float(np.min(ms)), 6)
-        out_extra["back_to_back_ms_mean"] = round(b2b_ms, 6)
-        out_extra["per_launch_reset_ms_median_events_without_system_fence"] = round(
-            nofence_ms(strat, (m, n, nnz, W["rp"], W["ci"], W["v"]), x, y, y0, 20, alpha, beta), 6)
-        _cold = cold_ms(torch, strat, (m, n, nnz, W["rp"], W["ci"], W["v"]), x, y, y0, 20, alpha, beta)
-        if _cold is not None:
-            out_extra["per_launch_cold_ms_median"] = round(_cold, 6)
+        ev_ms = kernel_ms = None
+        if args.full:
+            # the reference harness's protocol (csr_spmv.hpp:66-74): y reset by a device copy before every launch, one event pair
+            # per launch, median -- roofline.per_launch_protocol (rounds 1-4 quoted roofline.frac on it; since round 5 roofline.frac is the timed
+            # region's back-to-back figure: ROOFLINE_DEFINITION above, frozen)
+            ms = spmv_acc_amd.time_spmv(strat, max(20, min(args.steps, 50)), alpha, beta, m, n, nnz, W["rp"], W["ci"], W["v"], x, y, y0=y0)
+            ev_ms = float(np.median(ms))
+            # the same protocol with the library's kernel clock on: each launch's own start / stop timestamps
+            ev2, kn_ms, kn_launches = spmv_acc_amd.time_spmv_kernels(strat, max(20, min(args.steps, 50)), alpha, beta, m, n, nnz, W["rp"], W["ci"], W["v"], x, y, y0=y0)
+            kernel_ms = float(np.median(kn_ms))
+            out_extra["kernel_clock_ms_median"] = round(kernel_ms, 6)
+            out_extra["kernel_clock_launches_per_step"] = int(np.median(kn_launches))
+            out_extra["per_launch_reset_ms_median_under_kernel_clock"] = round(float(np.median(ev2)), 6)
+            out_extra["per_launch_reset_ms_median"] = round(ev_ms, 6)
+            out_extra["per_launch_reset_ms_min"] = round(float(np.min(ms)), 6)
+            out_extra["back_to_back_ms_mean"] = round(b2b_ms, 6)
+            out_extra["per_launch_reset_ms_median_events_without_system_fence"] = round(
+                nofence_ms(strat, (m, n, nnz, W["rp"], W["ci"], W["v"]), x, y, y0, 20, alpha, beta), 6)
+            _cold = cold_ms(torch, strat, (m, n, nnz, W["rp"], W["ci"], W["v"]), x, y, y0, 20, alpha, beta)
+            if _cold is not None:
+                out_extra["per_launch_cold_ms_median"] = round(_cold, 6)
     elif args.exchange == "ghost":
         # square workloads only: x partitioned like the rows, x <- alpha * A * x, each rank receiving just the entries its
         # columns reference (BASELINE configs[4]: 4 + 3 doubles per neighbour instead of an allgather of 256 MB slices)
@@ -1056,8 +1107,11 @@ def main():
             for _ in range(args.steps):
                 eng.iterate(alpha)
 
-        wall, walls = median_region(ghost_region, REGION_REPS, sync_all)
-        out_extra["region_reps"] = REGION_REPS
+        reps = REGION_REPS if args.full else 1
+        wall, walls = median_region(ghost_region, reps, sync_all)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(torch, args.dump_outputs, eng.x_ext[: eng.n_local])  # (what iterate() returns: this rank's slice of the new x)
+        out_extra["region_reps"] = reps
         xe = eng.x_ext.clone()
         ms = spmv_acc_amd.time_spmv(strat, min(args.steps, 50), alpha, beta, m, eng.n_local + eng.n_ghost, nnz, W["rp"],
                                     eng.cols_local, W["v"], xe, y)
@@ -1078,11 +1132,11 @@ def main():
             return float(t.item())
 
         wall, ev_ms, extra = sharded_leg(torch, dist, args, W, x, y0, alpha, beta, rank, world, device, backend, force_dist,
-                                         args.steps, args.warmup, time_left=time_left)
+                                         args.steps, args.warmup, time_left=time_left, dump_dir=args.dump_outputs)
         out_extra.update(extra)
         if backend == "nccl":
             out_extra["rccl"] = rccl_debug_summary(rank)
-        if args.workload == "hardesty3" and args.scale == 1.0 and not args.no_legs:
+        if args.full and args.workload == "hardesty3" and args.scale == 1.0 and not args.no_legs:
             # Side legs under the run's wall-clock allowance (SPMV_ACC_BENCH_BUDGET_S, default 420 s; the decision is collective -- the minimum over
             # ranks): a slow exchange must not cost the run its line by eating the driver's timeout.
             if time_left() > 150.0:
@@ -1189,8 +1243,8 @@ def main():
     roofline.update({
         "unit_note": "algorithmic bytes / launch time; a working set of <= 256 MB is served by the Infinity Cache between "
                      "launches, so small matrices can show more than the HBM rate -- it is a rate of useful bytes, not a PMC reading",
-        "protocol": "hipEvents around the timed region's K back-to-back launches on the library stream, per launch, median of the repetitions"
-                    if not dist_leg else "per-launch events around the local SpMV, y not reset",
+        "protocol": "hipEvents around the timed region's K back-to-back launches on the library stream, per launch, "
+                    + ("median of the repetitions" if args.full else "one region") if not dist_leg else "per-launch events around the local SpMV, y not reset",
         "traffic": pmc_traffic(args.workload, strat) if args.scale == 1.0 else None,
         "traffic_lower_bound": pmc_traffic(args.workload, strat, "lower_bound_bytes") if args.scale == 1.0 else None,
         "traffic_source": "profiles/pmc_traffic.json (builder-run rocprofv3 --pmc passes, tools/profile_round.sh; not measured by this run)"})
@@ -1205,22 +1259,24 @@ def main():
         "roofline": roofline,
         "protocol": "value / ms_per_step / roofline: K back-to-back SpMVs on one matrix resident in HBM (a solver loop: y is iterated in place, never reset; "
                     "consecutive SpMVs on a plan walk the matrix in alternating directions -- library default, tunable zigzag), wall clock and event time of "
-                    "the same region, median of the repetitions.  Every extra leg's us / frac and roofline.per_launch_protocol: the reference harness's "
-                    "protocol (csr_spmv.hpp:66-74: y reset before each launch, one event pair per launch, median), with the kernel-clock and "
-                    "back-to-back figures beside it",
-        "ref_formula_gibps": round(synth.reference_bytes(m, nnz) / 2**30 / (ev_ms * 1e-3), 2),
-        "gflops_kernel_only_per_gpu": round(2.0 * nnz / (kernel_ms * 1e-3) / 1e9, 3),
+                    "the same region, median of the repetitions (--full; one region otherwise).  Every extra leg's us / frac and "
+                    "roofline.per_launch_protocol (--full): the reference harness's protocol (csr_spmv.hpp:66-74: y reset before each launch, one "
+                    "event pair per launch, median), with the kernel-clock and back-to-back figures beside it",
     }
+    if ev_ms is not None:
+        result["ref_formula_gibps"] = round(synth.reference_bytes(m, nnz) / 2**30 / (ev_ms * 1e-3), 2)
+    if kernel_ms is not None:
+        result["gflops_kernel_only_per_gpu"] = round(2.0 * nnz / (kernel_ms * 1e-3) / 1e9, 3)
     result.update(out_extra)
     info = spmv_acc_amd.query_plan(W["rp"], m) if args.exchange != "ghost" else None
     if info:  # what the first call measured and kept for this matrix (kernel family: 0 fixed row blocks, 1 row-block-plus, 2 flat)
         result["plan"] = {k: info[k] for k in ("stream_policy", "adaptive_family", "flat_fixup", "plus_blocks", "flat_tiles", "slab_passes", "settled", "last_kernel", "col16")}
-    if rank == 0:
+    if rank == 0 and args.full:
         result["copy_ceiling_gbs"] = round(copy_ceiling_gbs(torch, device), 1)
         # the same achieved rates against what THIS box copies at (boxes of this pool read 6.25 .. 6.66 TB/s; the large sweep stand-ins
         # follow it, and with them the >= 0.70 count): informational, `roofline.frac` stays algorithmic bytes / time / 8 TB/s
         result["roofline"]["frac_of_copy_ceiling"] = round(result["roofline"]["achieved"] / result["copy_ceiling_gbs"], 4)
-    if rank == 0 and world == 1 and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_legs:
         # What the per-launch protocol costs before a single byte of a matrix moves: a 256-row diagonal matrix (one workgroup's
         # worth of work) under the same two protocols.  The small sweep matrices sit a few microseconds above this floor.
         tm = 256
@@ -1243,7 +1299,7 @@ def main():
                                   "back_to_back_us_mean": round(f_b2b * 1e3, 2),
                                   "per_launch_reset_us_median_events_without_system_fence": round(f_nf * 1e3, 2)}
         spmv_acc_amd.release_plans(trp)
-    if rank == 0 and world == 1 and args.workload == "hardesty3" and args.scale == 1.0 and not args.no_sensitivity:
+    if args.full and rank == 0 and world == 1 and args.workload == "hardesty3" and args.scale == 1.0 and not args.no_sensitivity:
         # Same dimensions and row lengths, none of the stand-in's 10 % uniformly random columns (SURVEY.md 8d prescribes
         # them; the real matrix is not available): shows live how much of `roofline.frac` is the gather sector cost.
         m2, n2, nnz2 = synth.LARGE_SET["Hardesty3"]
@@ -1259,12 +1315,12 @@ def main():
                                  "frac_back_to_back": round(b_alg / (t2b * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
         spmv_acc_amd.release_plans(rp2)
         del rp2, ci2, v2, y2
-    if rank == 0 and world == 1 and args.workload == "hardesty3" and args.scale == 1.0 and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and args.workload == "hardesty3" and args.scale == 1.0 and not args.no_legs:
         result.update(extra_legs(torch, device, (m, n, nnz, W["rp"], W["ci"], W["v"]), in_process=args.legs_in_process))
         ceiling_frac = result["copy_ceiling_gbs"] / HBM_PEAK_GBS
         for s in ("flat", "adaptive"):
             result["sweep_summary"][s]["median_frac_of_copy_ceiling"] = round(result["sweep_summary"][s]["median_frac"] / ceiling_frac, 4)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(W, x, y0, args.cpu_seconds)
     elif rank == 0:
         result["cpu_baseline"] = None

@@ -10,6 +10,9 @@ for the analysis goldens, oracle/_ref/libref_analyze.so built from /root/referen
   analysis_cases.npz  rowptr inputs + break_points / first_block_of_row / block count produced by the
                       REFERENCE's own csr_adaptive_plus_analyze.cpp (compiled unmodified into oracle/_ref).
   breakpoint_cases.npz rowptr inputs + break points from our restatement of flat_imp.inl:108-131.
+  reader_cases.npz    small matrix files + what the REFERENCE's own readers parse from them (oracle/_ref).
+  reference_random_cases.npz  what oracle/_ref's analysis and readers return on the random cases of two tests
+                      (the inputs are regenerated from their seeds by the tests).
 Fixtures are data only (inputs and expected outputs).
 """
 import os
@@ -202,3 +205,37 @@ def reader_cases():
 if __name__ == "__main__":
     np.savez_compressed(os.path.join(HERE, "reader_cases.npz"), **reader_cases())
     print("reader_cases.npz", os.path.getsize(os.path.join(HERE, "reader_cases.npz")), "bytes")
+
+
+# ---- what the reference's compiled analysis and readers return on the random cases of two tests ----------------------------------------
+def reference_random_cases():
+    """reference_random_cases.npz: the outputs of oracle/_ref (both libraries) on the cases of tests/test_oracle.py::
+    test_analysis_against_compiled_reference (oracle_lib.random_rowptr_cases) and tests/test_cli_io.py::test_readers_match_compiled_reference_random
+    (test_cli_io.random_reader_files), so that those tests run where oracle/_ref cannot be built."""
+    import pathlib
+    import tempfile
+
+    import test_cli_io
+
+    assert oracle_lib.ref() is not None and oracle_lib.ref_readers() is not None, "oracle/_ref not built"
+    out = {}
+    params = oracle_lib.REF_ANALYSIS_PARAMS
+    blocks = np.zeros((oracle_lib.REF_ANALYSIS_TRIALS, len(params)), dtype=np.int32)
+    for trial, rp in enumerate(oracle_lib.random_rowptr_cases()):
+        for k, (threads, vec, min_nnz) in enumerate(params):
+            b, bp, fbr = oracle_lib.ref_adaptive_plus_analyze(rp, min_nnz, threads, vec)
+            blocks[trial, k] = b
+            out[f"analysis__{trial}__{k}__bp"], out[f"analysis__{trial}__{k}__fbr"] = bp, fbr
+    out["analysis__blocks"] = blocks
+    with tempfile.TemporaryDirectory() as d:
+        for trial, path, fmt in test_cli_io.random_reader_files(pathlib.Path(d)):
+            rows, cols, nnz, rp, ci, v, x = oracle_lib.ref_read_matrix(path, fmt)
+            key = f"readers__{trial}__{fmt}"
+            out[f"{key}__dims"] = np.array([rows, cols, nnz], dtype=np.int64)
+            out[f"{key}__rowptr"], out[f"{key}__colidx"], out[f"{key}__values"], out[f"{key}__x"] = rp, ci, v, x
+    return out
+
+
+if __name__ == "__main__":
+    np.savez_compressed(os.path.join(HERE, "reference_random_cases.npz"), **reference_random_cases())
+    print("reference_random_cases.npz", os.path.getsize(os.path.join(HERE, "reference_random_cases.npz")), "bytes")

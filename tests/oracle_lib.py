@@ -211,6 +211,32 @@ def ref_adaptive_plus_analyze(rowptr, min_nnz=2048, threads=512, vec=1):
     return _analyze(ref().ref_adaptive_plus_analyze, rowptr, min_nnz, threads, vec, True)
 
 
+# The random row-length laws tests/test_oracle.py::test_analysis_against_compiled_reference runs the analysis on, with the (threads, vec,
+# min_nnz) triples; tests/golden/make_golden.py stores the compiled reference's outputs for exactly these cases.
+REF_ANALYSIS_SEED, REF_ANALYSIS_TRIALS = 99, 120
+REF_ANALYSIS_PARAMS = ((512, 1, 2048), (512, 4, 2048), (256, 16, 1024), (1024, 64, 4096))
+
+
+def random_rowptr_cases(seed=REF_ANALYSIS_SEED, trials=REF_ANALYSIS_TRIALS, m_max=2500):
+    """`trials` int32 rowptrs, cycling through four row-length laws: short, Pareto, a few very long rows, wide uniform."""
+    rng = np.random.default_rng(seed)
+    for trial in range(trials):
+        m = int(rng.integers(1, m_max))
+        kind = trial % 4
+        if kind == 0:
+            lens = rng.integers(0, 12, m)
+        elif kind == 1:
+            lens = np.minimum((rng.pareto(1.2, m) * 3).astype(np.int64), 20000)
+        elif kind == 2:
+            lens = rng.integers(0, 3, m)
+            lens[rng.integers(0, m, 3)] = rng.integers(2000, 30000, 3)
+        else:
+            lens = rng.integers(0, 700, m)
+        rp = np.zeros(m + 1, dtype=np.int32)
+        np.cumsum(lens, out=rp[1:])
+        yield rp
+
+
 def adaptive_pick(rowptr):
     rowptr = _c(rowptr, np.int32)
     return lib().oracle_adaptive_pick(rowptr.size - 1, _i(rowptr))

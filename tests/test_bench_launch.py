@@ -176,3 +176,23 @@ def test_roofline_frac_keeps_its_source():
     assert '"us": round(reset_ms * 1e3, 2), "frac": frac(reset_ms)' in src
     assert 'roofline = roofline_block(b_alg, b2b_ms, kernel_ms, ev_ms, out_extra.get("per_launch_cold_ms_median"))' in src
     assert '"ge_0.70": sum(1 for r in sweep.values() if r[s]["frac"] >= 0.70)' in src
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs: y is written whole up to DUMP_MAX_ROWS rows, else as the same seeded, ascending sample of rows on every run and build;
+    float64, at most 64 MB at the headline's length."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    assert bench.dump_rows(1000) is None
+    m = 8_217_820
+    rows = bench.dump_rows(m)
+    assert rows.size == bench.DUMP_MAX_ROWS and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < m
+    assert np.array_equal(rows, bench.dump_rows(m)) and 8 * rows.size <= 64_000_000
+    y = torch.arange(m, dtype=torch.float64)
+    bench.dump_outputs(torch, str(tmp_path / "out"), y)
+    got = np.load(tmp_path / "out" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, rows.astype(np.float64))
+    bench.dump_outputs(torch, str(tmp_path / "small"), y[:1000])
+    assert np.array_equal(np.load(tmp_path / "small" / "y.npy"), np.arange(1000.0))

@@ -365,10 +365,11 @@ def test_convert_bin2_writes_what_the_reference_converter_writes(cli, tmp_path, 
     assert subprocess.run([cli, pc, "-f", "csr", "--convert-bin2", "/nonexistent-dir/x.bin2"], capture_output=True).returncode == 3
 
 
-def test_readers_match_compiled_reference_random(cli, tmp_path, oracle):
-    if oracle.ref_readers() is None:
-        pytest.skip("oracle/_ref/libref_readers.so not built (no /root/reference on this machine)")
+def random_reader_files(tmp_path):
+    """Six random matrices, each as .csr text, bin2 and MatrixMarket under tmp_path: [(trial, path, fmt)].  tests/golden/make_golden.py stores
+    what the reference's compiled readers parse from exactly these files."""
     rng = np.random.default_rng(123)
+    files = []
     for trial in range(6):
         m, n = int(rng.integers(1, 400)), int(rng.integers(1, 400))
         rowptr, cols, vals = synth.random_csr(m, n, int(rng.integers(1, 9)), seed=500 + trial,
@@ -388,17 +389,29 @@ def test_readers_match_compiled_reference_random(cli, tmp_path, oracle):
             f.write("%d %d %d\n" % (m, n, len(A)))
             for (r, c), val in A.items():
                 f.write("%d %d %.17g\n" % (r, c, val))
-        for path, fmt in ((pc, "csr"), (pb, "bin2"), (pm, "mtx")):
-            want = oracle.ref_read_matrix(path, fmt)
-            out = path + ".dump"
-            rr = subprocess.run([cli, path, "-f", fmt, "--dump-bin", out], capture_output=True, text=True)
-            assert rr.returncode == 0, rr.stderr
-            got = _read_dump(out)
-            assert got[:3] == want[:3], (trial, fmt)
-            for a, b in zip(got[3:6], want[3:6]):
-                assert np.array_equal(a, b), (trial, fmt)
-            if fmt == "csr":
-                assert np.array_equal(got[6], want[6])
+        files += [(trial, pc, "csr"), (trial, pb, "bin2"), (trial, pm, "mtx")]
+    return files
+
+
+def test_readers_match_compiled_reference_random(cli, tmp_path, oracle):
+    """Our readers against what the reference's compiled readers (oracle/_ref/libref_readers.so) parse from random files, stored in
+    tests/golden/reference_random_cases.npz; where oracle/_ref is built, the stored results are checked against it as well."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_random_cases.npz"))
+    for trial, path, fmt in random_reader_files(tmp_path):
+        key = f"readers__{trial}__{fmt}"
+        want = tuple(int(t) for t in g[f"{key}__dims"]) + tuple(g[f"{key}__{k}"] for k in ("rowptr", "colidx", "values", "x"))
+        if oracle.ref_readers() is not None:
+            ref = oracle.ref_read_matrix(path, fmt)
+            assert ref[:3] == want[:3] and all(np.array_equal(a, b) for a, b in zip(ref[3:], want[3:])), (trial, fmt, "stored fixture")
+        out = path + ".dump"
+        rr = subprocess.run([cli, path, "-f", fmt, "--dump-bin", out], capture_output=True, text=True)
+        assert rr.returncode == 0, rr.stderr
+        got = _read_dump(out)
+        assert got[:3] == want[:3], (trial, fmt)
+        for a, b in zip(got[3:6], want[3:6]):
+            assert np.array_equal(a, b), (trial, fmt)
+        if fmt == "csr":
+            assert np.array_equal(got[6], want[6])
 
 
 def test_readers_reject_malformed_files_under_sanitizers(tmp_path):

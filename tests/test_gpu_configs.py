@@ -293,7 +293,7 @@ def test_configs4_banded_shard_full_size(torch_dev, oracle):
 
 
 def test_bench_line_carries_every_baseline_config(torch_dev):
-    """The driver's command -- `python bench.py` with its defaults -- prints ONE SHORT JSON line on stdout (< 6000 bytes: the driver keeps
+    """The driver's command with every measurement -- `python bench.py --full` -- prints ONE SHORT JSON line on stdout (< 6000 bytes: the driver keeps
     an 8 KB tail; one short row per measurement, as statistics_logger.cpp:11-31 prints) whose headline is configs[1] with `roofline` and
     `cpu_baseline`, plus one figure per extra leg: configs[2] (`sweep`: 12 stand-ins -> [flat, adaptive] fractions), configs[3]
     (`rmat25`), configs[4] (`banded_shard`).  Every detail (both protocols per leg, the tile kernel alone, opt-in legs, notes) is in
@@ -307,7 +307,7 @@ def test_bench_line_carries_every_baseline_config(torch_dev):
     full_path = os.path.join(root, "bench_full.json")
     if os.path.exists(full_path):
         os.remove(full_path)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "50", "--warmup", "5", "--cpu-seconds", "2"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "50", "--warmup", "5", "--full", "--cpu-seconds", "2"],
                          capture_output=True, text=True, check=True).stdout.strip().splitlines()
     assert len(out) == 1, out[:3]  # libraries' chatter goes to stderr
     assert len(out[0]) < 6000, len(out[0])

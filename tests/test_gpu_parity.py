@@ -545,11 +545,11 @@ def test_banded_shard_closed_form(torch_dev):
 
 
 def test_bench_contract_small(torch_dev):
-    """bench.py prints ONE JSON line with the driver's keys + roofline + cpu_baseline (reduced scale for speed)."""
+    """bench.py --full prints ONE JSON line with the driver's keys + roofline + cpu_baseline (reduced scale for speed)."""
     import json
     import sys
 
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--scale", "0.02",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--scale", "0.02", "--full",
                           "--cpu-seconds", "1"], capture_output=True, text=True, check=True).stdout.strip().splitlines()
     d = json.loads(out[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",

@@ -472,7 +472,7 @@ def test_ms_per_step_is_the_kernels_time(torch_dev):
     it) and the driver-timed value read 14 % below the kernel's.  `ms_per_step` is now the MEDIAN of REGION_REPS repetitions of a region that holds
     the K launches and nothing else (spmv_acc_time_spmv_region): at the driver's own arguments it stays within 3 % of the event time of the same
     launches, and the line says how many repetitions it is the median of."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-legs", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-legs", "--no-cpu-baseline",
                         "--no-sensitivity"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -483,6 +483,32 @@ def test_ms_per_step_is_the_kernels_time(torch_dev):
     assert line["ms_per_step"] <= 1.03 * ev, (line["ms_per_step"], ev, full.get("ms_per_step_wall_all"), full.get("ms_per_step_events_all"))
     assert abs(line["ms_per_step_events"] - ev) < 1e-9 and b2b["frac"] > 0.3
     assert abs(line["value"] - 2.0 * line["config"]["nnz_per_gpu"] / (line["ms_per_step"] * 1e-3) / 1e9) / line["value"] < 1e-3
+
+
+def test_plain_run_times_k_steps_and_dumps_their_result(torch_dev, oracle, tmp_path):
+    """A plain `bench.py --steps K --warmup W` times ONE region of exactly K steps and measures nothing else (no CPU baseline, no legs); with
+    --dump-outputs DIR it writes the y those K steps left, which is y0 + K * A x on the run's seeded inputs."""
+    torch = torch_dev
+    steps, scale = 7, 0.02
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--scale", str(scale),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == steps and line["region_reps"] == 1 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    assert "sweep" not in line and "copy_ceiling_gbs" not in line and line["roofline"]["frac"] > 0
+    assert abs(line["value"] - 2.0 * line["config"]["nnz_per_gpu"] / (line["ms_per_step"] * 1e-3) / 1e9) / line["value"] < 1e-3
+    got = np.load(tmp_path / "y.npy")
+    m, n, nnz, rp, ci, v = synth.hardesty3_like_torch(device="cuda", seed=0xC2, scale=scale)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(1234)  # (bench.py's inputs)
+    x = torch.rand(n, generator=gen, device="cuda", dtype=torch.float64) * 2 - 1
+    y0 = torch.rand(m, generator=gen, device="cuda", dtype=torch.float64) * 2 - 1
+    assert got.dtype == np.float64 and got.shape == (m,)
+    h = [t.cpu().numpy() for t in (rp, ci, v, x, y0)]
+    ax = oracle.host_spmv(1.0, 0.0, h[0], h[1], h[2], h[3], np.zeros(m))
+    mag = oracle.host_spmv(1.0, 0.0, h[0], h[1], np.abs(h[2]), np.abs(h[3]), np.zeros(m))
+    want = h[4] + steps * ax
+    assert np.all(np.abs(got - want) <= SCALED_TOL * (np.abs(h[4]) + steps * mag) + 1e-300)
 
 
 def test_kernel_clock_reads_the_kernels_own_time(torch_dev, oracle, hiplib):

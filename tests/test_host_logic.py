@@ -291,37 +291,6 @@ def test_round3_switches_and_entry_points_without_a_gpu(hiplib, tmp_path):
     hiplib.spmv_acc_clear_error()
 
 
-def test_reference_flat_benchmark_tu_builds_against_include(hiplib, tmp_path):
-    """The drop-in pinned with the reference's OWN translation unit: benchmark/flat/spmv_acc_flat.cpp (the benchmark's private flat copy: it
-    launches pre_calc_break_point / pre_calc_break_point_v2 itself and expands FLAT_KERNEL_WRAPPER / FLAT_KERNEL_ONE_PASS_WRAPPER,
-    spmv_acc_flat.cpp:14-15,34,38,65-71) and benchmark/utils/benchmark_time.cpp are compiled UNMODIFIED, from where they lie, with this
-    repository's include/ standing where the reference's src/acc would (benchmark_spmv_acc.hpp:14-25 names the same header paths), and linked
-    with libspmv_acc.so and a main that names flat_sparse_spmv<V1>, <V2>, adaptive_flat_sparse_spmv<V1> and segment_sum_flat_sparse_spmv.
-    Runs where /root/reference exists (this container); nothing reference-derived travels to the GPU box."""
-    ref = "/root/reference"
-    tu = os.path.join(ref, "benchmark", "flat", "spmv_acc_flat.cpp")
-    if not os.path.exists(tu) or not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("the reference tree (or hipcc) is not on this machine")
-    libdir = os.path.dirname(spmv_acc_amd.LIB_PATH)
-    exe = str(tmp_path / "ref_flat_tu")
-    cmd = ["/opt/rocm/bin/hipcc", "-w", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"),
-           "-I", os.path.join(ref, "benchmark"), "-I", os.path.join(ref, "cli"),
-           os.path.join(ROOT, "tests", "cxx", "ref_flat_tu_main.cpp"), tu, os.path.join(ref, "benchmark", "utils", "benchmark_time.cpp"),
-           "-L", libdir, "-lspmv_acc", f"-Wl,-rpath,{libdir}", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    # every undefined symbol of the executable that belongs to this library is one the library defines (the link above already failed otherwise);
-    # what the reference TU needs from us at link time is the strategy entry its launch macros forward to
-    undef = subprocess.run(["nm", "-u", "-C", exe], capture_output=True, text=True, check=True).stdout
-    assert "spmv_acc_csr_spmv_strategy" in undef
-    defined = subprocess.run(["nm", "-C", "--defined-only", exe], capture_output=True, text=True, check=True).stdout
-    for name in ("flat_sparse_spmv<1>", "flat_sparse_spmv<2>", "adaptive_flat_sparse_spmv<1>", "adaptive_flat_sparse_spmv<2>",
-                 "segment_sum_flat_sparse_spmv", "BenchmarkTime::set_time"):
-        assert name in defined, name
-    # it loads and runs to main() without a GPU (the SpMV calls sit behind a false test)
-    assert subprocess.run([exe], capture_output=True, timeout=60).returncode == 0
-
-
 def test_every_size_threshold_names_a_test():
     """tests/size_thresholds.py: every size-selected branch of the engine is registered with the test(s) that cross it; every named constant of the
     engine's sources is either such a rule or listed as geometry.  (Round 4's wrong-result regression sat behind a size rule no test crossed.)"""

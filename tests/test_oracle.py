@@ -1,5 +1,5 @@
 """CPU suite: the oracle (oracle/spmv_oracle.c) against golden vectors, an independent implementation
-(scipy) and closed-form cases; the oracle's analysis against the compiled reference (oracle/_ref)."""
+(scipy) and closed-form cases; the oracle's analysis against the compiled reference's stored outputs."""
 import os
 
 import numpy as np
@@ -173,27 +173,18 @@ def test_analysis_golden_from_reference(oracle):
 
 
 def test_analysis_against_compiled_reference(oracle):
-    if oracle.ref() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    rng = np.random.default_rng(99)
-    for trial in range(120):
-        m = int(rng.integers(1, 2500))
-        kind = trial % 4
-        if kind == 0:
-            lens = rng.integers(0, 12, m)
-        elif kind == 1:
-            lens = np.minimum((rng.pareto(1.2, m) * 3).astype(np.int64), 20000)
-        elif kind == 2:
-            lens = rng.integers(0, 3, m)
-            lens[rng.integers(0, m, 3)] = rng.integers(2000, 30000, 3)
-        else:
-            lens = rng.integers(0, 700, m)
-        rp = np.zeros(m + 1, dtype=np.int32)
-        np.cumsum(lens, out=rp[1:])
-        for threads, vec, min_nnz in ((512, 1, 2048), (512, 4, 2048), (256, 16, 1024), (1024, 64, 4096)):
+    """Our restatement against the reference's own analysis (csr_adaptive_plus_analyze.cpp compiled into oracle/_ref) on 120 random row-length
+    laws: the reference's outputs are stored in tests/golden/reference_random_cases.npz (tests/golden/make_golden.py); where oracle/_ref is
+    built, the stored outputs are checked against it as well."""
+    g = np.load(os.path.join(GOLD, "reference_random_cases.npz"))
+    for trial, rp in enumerate(oracle.random_rowptr_cases()):
+        for k, (threads, vec, min_nnz) in enumerate(oracle.REF_ANALYSIS_PARAMS):
             a = oracle.adaptive_plus_analyze(rp, min_nnz, threads, vec)
-            b = oracle.ref_adaptive_plus_analyze(rp, min_nnz, threads, vec)
-            assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+            b = (int(g["analysis__blocks"][trial, k]), g[f"analysis__{trial}__{k}__bp"], g[f"analysis__{trial}__{k}__fbr"])
+            assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), (trial, k)
+            if oracle.ref() is not None:
+                c = oracle.ref_adaptive_plus_analyze(rp, min_nnz, threads, vec)
+                assert c[0] == b[0] and np.array_equal(c[1], b[1]) and np.array_equal(c[2], b[2]), (trial, k, "stored fixture")
 
 
 def test_strategy_pickers(oracle):

@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "[profile_round] kernel trace"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py "$@" --no-cpu-baseline --no-sensitivity > $OUT/bench_under_trace.json 2> $OUT/trace.log || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py "$@" --full --no-cpu-baseline --no-sensitivity > $OUT/bench_under_trace.json 2> $OUT/trace.log || exit 1
 # (bench.py measures its extra legs in child processes and rocprofv3 writes one summary per process: the parent's -- the lowest pid -- holds the timed region)
 S=$(find $OUT/trace -name "*kernel_stats.csv" | awk -F/ '{f=$NF; sub(/_kernel_stats.csv/,"",f); print f+0, $0}' | sort -n | head -1 | cut -d" " -f2-)
 { head -1 $S; grep -E "spmv_acc" $S; } > $OUT/kernel_stats_spmv.csv
@@ -30,7 +30,7 @@ if [ "$C16" -ge 0 ] 2>/dev/null; then export SPMV_ACC_TUNABLES="col16=$C16${SPMV
 echo "[profile_round] counter passes with SPMV_ACC_TUNABLES=$SPMV_ACC_TUNABLES"
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "[profile_round] pmc $c"
-  timeout -k 10 500 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -- python3 $R/bench.py "$@" --no-cpu-baseline --no-legs --no-sensitivity --steps 20 --warmup 5 > $OUT/bench_under_$c.json 2> $OUT/pmc_$c.log || exit 1
+  timeout -k 10 500 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -- python3 $R/bench.py "$@" --full --no-cpu-baseline --no-legs --no-sensitivity --steps 20 --warmup 5 > $OUT/bench_under_$c.json 2> $OUT/pmc_$c.log || exit 1
   F=$(find $OUT/pmc_$c -name "*counter_collection.csv" | head -1)
   python3 - "$F" "$c" > $OUT/pmc_$c.summary.txt <<'PY'
 import csv, sys, collections
