@@ -92,6 +92,25 @@ void spmv_acc_csr_spmv_oop(int strategy, int trans, double alpha, double beta, i
                            const int *d_rowptr, const int *d_colindex, const double *d_value, const double *dx,
                            const double *dy_in, double *dy_out);
 
+/* ---- CSR SpMM: one matrix, k vectors (new) --------------------------------------------------------------------------------
+ * replaces: nothing in the reference (it has no multi-vector product; its callers make k SpMV calls, each re-reading the matrix).
+ * Y = alpha * A * X + beta * Y for k dense vectors, one pass over the matrix per panel of up to 32 columns.
+ *   Row-major:    X[i * ldx + j] (i < n, j < k, ldx >= k),  Y[r * ldy + j] (ldy >= k).
+ *   Column-major: X[j * ldx + i] (ldx >= n),                Y[j * ldy + r] (ldy >= m).
+ * Offsets are 64-bit; X and Y may be views that are only 8-B aligned (odd ld, a column slice).  X and Y must not overlap (not
+ * detected).  Asynchronous on the calling thread's library stream; h_rowptr optional, as for spmv_acc_csr_spmv.
+ * k == 0 or m == 0: nothing, returns SPMV_ACC_OK.  nnz == 0 or n == 0: Y = beta * Y.  beta == 0: Y is never read (NaNs in it do not
+ * propagate).  Only the first k entries of each Y row (row-major) / column (column-major) are written; the padding up to ldy is not
+ * touched.  A bad layout, k < 0, an ld below its minimum or a null pointer where data is needed: SPMV_ACC_ERR_BAD_ARGUMENT, nothing
+ * is launched.  KERNEL_STRATEGY does not apply (one kernel family), except that k == 1 with contiguous vectors is served by the
+ * SpMV path under the active strategy: bitwise what spmv_acc_csr_spmv gives.  The matrix shares its plan with SpMV calls; the first
+ * uncaptured SpMM call on a matrix builds the plan's SpMM tables (from rowptr), later calls only launch and may be captured.
+ * Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error). */
+enum spmv_acc_layout { SPMV_ACC_ROW_MAJOR = 0, SPMV_ACC_COL_MAJOR = 1 };
+int spmv_acc_csr_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz, const int *h_rowptr,
+                      const int *d_rowptr, const int *d_colindex, const double *d_value,
+                      const double *dX, long long ldx, double *dY, long long ldy);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

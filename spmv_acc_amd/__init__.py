@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_query_plan_beta0", "spmv_acc_query_plan_slab_passes", "spmv_acc_shard_create", "spmv_acc_shard_step", "spmv_acc_shard_pipeline",
     "spmv_acc_shard_destroy", "spmv_acc_rccl_comm_init_all", "spmv_acc_rccl_comm_destroy", "spmv_acc_set_tune_cache",
     "spmv_acc_prepare_beta", "spmv_acc_time_spmv_events", "spmv_acc_refresh_values", "spmv_acc_time_spmv_region", "spmv_acc_query_plan_last_kernel", "spmv_acc_time_spmv_kernels",
+    "spmv_acc_csr_spmm",
 )
 
 _lib = None
@@ -132,6 +133,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_prepare_beta.argtypes = [ci, cd, ci, ci, ci, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     lib.spmv_acc_shard_prepare.argtypes = [vp, cd, vp]
     lib.spmv_acc_csr_spmv_chunks.argtypes = [ci, cd, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    ll = ctypes.c_longlong
+    lib.spmv_acc_csr_spmm.argtypes = [ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp, vp, ll, vp, ll]
+    lib.spmv_acc_csr_spmm.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -230,6 +234,60 @@ def csr_spmv(alpha: float, beta: float, m: int, n: int, nnz: int, rowptr, colind
         lib.spmv_acc_csr_spmv(*args)
     else:
         lib.spmv_acc_csr_spmv_strategy(strategy_id(strategy), *args)
+    _check(lib)
+
+
+SPMM_ROW_MAJOR, SPMM_COL_MAJOR = 0, 1  # enum spmv_acc_layout
+
+
+def _spmm_layouts(name, t, rows: int, k: int):
+    """The layouts (with their leading dimension) an (rows, k) view can be passed as: {layout: ld}."""
+    s0, s1 = t.stride()
+    out = {}
+    if (s1 == 1 or k <= 1) and s0 >= max(k, 1):
+        out[SPMM_ROW_MAJOR] = s0
+    if (s0 == 1 or rows <= 1) and s1 >= max(rows, 1):
+        out[SPMM_COL_MAJOR] = s1
+    if not out and rows > 0 and k > 0:
+        raise SpmvAccError(f"{name}: strides {tuple(t.stride())} of a ({rows}, {k}) view are neither row-major (unit stride on dim 1, "
+                           f"leading dimension >= k) nor column-major (unit stride on dim 0, leading dimension >= {rows})")
+    return out
+
+
+def csr_spmm(alpha: float, beta: float, m: int, n: int, nnz: int, rowptr, colindex, value, X, Y, h_rowptr=None) -> None:
+    """Y = alpha*A*X + beta*Y for the k columns of X (spmv_acc_csr_spmm, async on torch's current stream).  X: (n, k) float64 GPU tensor,
+    Y: (m, k); both row-major (unit stride on dim 1) or both column-major (unit stride on dim 0), views with a larger leading dimension
+    included.  The layout and leading dimensions are read from the strides; any other stride pattern is refused."""
+    lib = load_library()
+    for name, t, rows in (("X", X, n), ("Y", Y, m)):
+        if not hasattr(t, "is_cuda") or not hasattr(t, "stride"):
+            raise SpmvAccError(f"{name}: a torch tensor on the GPU is required")
+        if not t.is_cuda:
+            raise SpmvAccError(f"{name}: device pointers required, tensor is not on the GPU (no CPU fallback)")
+        if str(t.dtype) != "torch.float64":
+            raise SpmvAccError(f"{name}: dtype {t.dtype}, the library reads torch.float64")
+        if t.dim() != 2 or t.shape[0] != rows:
+            raise SpmvAccError(f"{name}: shape {tuple(t.shape)}, expected ({rows}, k)")
+    if X.shape[1] != Y.shape[1]:
+        raise SpmvAccError(f"X has {X.shape[1]} columns, Y has {Y.shape[1]}")
+    if X.device != Y.device:
+        raise SpmvAccError(f"Y: on {Y.device}, X on {X.device}")
+    k = int(X.shape[1])
+    lx, ly = _spmm_layouts("X", X, n, k), _spmm_layouts("Y", Y, m, k)
+    if not lx or not ly:  # (an empty view: nothing is computed, any consistent arguments do)
+        layout, ldx, ldy = SPMM_ROW_MAJOR, k, k
+    else:
+        both = [lay for lay in (SPMM_ROW_MAJOR, SPMM_COL_MAJOR) if lay in lx and lay in ly]
+        if not both:
+            raise SpmvAccError("X and Y must share one layout (both row-major or both column-major)")
+        layout = both[0]
+        ldx, ldy = lx[layout], ly[layout]
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", max(nnz, 0)), value=(value, "f64", max(nnz, 0)))
+    if hasattr(rowptr, "device") and rowptr.device != X.device:
+        raise SpmvAccError(f"X: on {X.device}, rowptr on {rowptr.device}")
+    lib.spmv_acc_set_stream(__import__("torch").cuda.current_stream(X.device).cuda_stream)
+    lib.spmv_acc_csr_spmm(layout, k, alpha, beta, m, n, nnz, _ptr(h_rowptr), _ptr(rowptr), _ptr(colindex), _ptr(value), _ptr(X), ldx,
+                          _ptr(Y), ldy)
     _check(lib)
 
 

@@ -191,6 +191,11 @@ void spmv_acc_csr_spmv_oop(int strategy, int trans, double alpha, double beta, i
            dy_out, dy_in);
 }
 
+int spmv_acc_csr_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz, const int *h_rowptr, const int *d_rowptr,
+                      const int *d_colindex, const double *d_value, const double *dX, long long ldx, double *dY, long long ldy) {
+  return run_spmm(layout, k, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dX, ldx, dY, ldy);
+}
+
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
                              const int *d_rowptr, const int *d_colindex, const double *d_value, const double *dx,
                              const double *dy_in, double *dy_out, void *const *streams, void *const *events) {

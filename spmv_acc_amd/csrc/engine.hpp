@@ -116,6 +116,10 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
               const int *d_rowptr, const int *d_colindex, const double *d_value, const double *dx, double *dy,
               const double *dy_in = nullptr);
 
+// One SpMM Y = alpha*A*X + beta*Y for k vectors (spmm.cpp; include/spmv_acc.h spmv_acc_csr_spmm): layout 0 row-major, 1 column-major.
+// Returns kOk or the error code it also leaves in the calling thread's error slot.
+int run_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz, const int *h_rowptr, const int *d_rowptr, const int *d_colindex,
+             const double *d_value, const double *dX, long long ldx, double *dY, long long ldy);
 // Drop cached plans (all, or those keyed on this rowptr).  Call when a matrix' structure changes in
 // place or its buffers are freed.
 void release_plans(const int *d_rowptr, int m_only = -1);

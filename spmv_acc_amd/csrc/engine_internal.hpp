@@ -177,6 +177,16 @@ struct Plan {
   int *d_pfbr = nullptr;
   double *d_ppartial = nullptr;
   void *d_pblk = nullptr;
+  // SpMM section (spmm.cpp): built from rowptr alone by the first uncaptured SpMM call; -1 not built, 0 no long rows, 1 long-row tables built.
+  // SpMM calls read and write nothing else of the plan but its ordering fields (last_stream, launched, order_event)
+  int spmm_state = -1;
+  SpmmLong spmm;
+  void free_spmm() {
+    for (void *q : {static_cast<void *>(spmm.rows), static_cast<void *>(spmm.first), static_cast<void *>(spmm.piece), static_cast<void *>(spmm.partial)})
+      if (q) (void)hipFree(q);
+    spmm = SpmmLong();
+    spmm_state = -1;
+  }
 
   ~Plan() {
     free_device();
@@ -239,6 +249,7 @@ struct Plan {
     free_flat();
     free_digest();
     free_col16();
+    free_spmm();
     if (d_pbp) (void)hipFree(d_pbp);
     if (d_pfbr) (void)hipFree(d_pfbr);
     if (d_ppartial) (void)hipFree(d_ppartial);

@@ -285,6 +285,26 @@ constexpr int kSlabCopyAfterCalls = 32; // the automatic slab-major copy is buil
 // dst = src over `bytes` (16-B granules) with the kernels' streaming load shape: the copy ceiling probe
 void launch_stream_copy(hipStream_t stream, void *dst, const void *src, long long bytes, bool non_temporal);
 
+// ---- CSR SpMM (k_spmm.hip; size rules in spmm.hpp) ----------------------------------------------------------------------------------
+// Y = alpha * A * X + beta * Y for one panel of kp <= kSpmmPanel columns; x / y point at the panel's first column.  Row-major: X(i, j) = x[i * ldx + j],
+// column-major: x[j * ldx + i] (Y alike with ldy).  Rows longer than kSpmmLongRow are skipped here: launch_spmm_long owns them.
+// The long rows of a plan, cut into pieces (spmm.cpp builds the tables from rowptr alone)
+struct SpmmLong {
+  int nlong = 0;             // rows longer than kSpmmLongRow
+  int npieces = 0;           // their pieces, row by row
+  int *rows = nullptr;       // nlong row ids (ascending)
+  int *first = nullptr;      // nlong + 1: row i owns pieces first[i] .. first[i + 1]
+  int *piece = nullptr;      // 2 * npieces: each piece's absolute non-zero range [begin, end)
+  double *partial = nullptr; // kSpmmPanel * npieces: the pieces' partial sums, column-major (a (row, column)'s pieces are contiguous)
+};
+int spmm_team_lanes(int kp); // row-major: lanes per row, two columns per lane (1, 2, 4, 8 or 16)
+void launch_spmm_rows(hipStream_t stream, const CsrDev &A, bool row_major, int kp, long long ldx, long long ldy, double alpha, double beta,
+                      const double *x, double *y);
+void launch_spmm_long(hipStream_t stream, const CsrDev &A, const SpmmLong &L, bool row_major, int kp, long long ldx, long long ldy, double alpha,
+                      double beta, const double *x, double *y);
+// Y = beta * Y over the m x k view (nnz == 0 or n == 0); beta == 0 writes zeros without reading Y
+void launch_spmm_scale(hipStream_t stream, int m, int k, bool row_major, long long ldy, double beta, double *y);
+
 // y[i] = beta * y[i] (used for m > 0, nnz == 0 and as a building block)
 void launch_scale_y(hipStream_t stream, int m, double beta, double *y, const double *yin = nullptr);
 void launch_validate_csr(hipStream_t stream, const CsrDev &A, int *d_flags); // *d_flags pre-zeroed; bits: see kernel
