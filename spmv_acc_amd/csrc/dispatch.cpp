@@ -55,21 +55,16 @@ bool run_flat(hipStream_t st, Plan &p, double alpha, double beta, const double *
       if (!probe_rowblock(p, rpb, st)) return false;
       p.flat_rowblock_choice = 0;
       if (p.rowblock_ok == 1) {
-        ++t_plan_work;
-        double *scratch = nullptr;
-        if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-        TuneTimer timer;
-        timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-        bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+        TimingPhase ph(st, p.A.m);
         float ms2[2] = {0.f, 0.f};
-        ok = ok && run_rowblock(st, p, nullptr, 1.0, trial_beta(), x, scratch, false); // (builds and tunes the row-block side)
+        bool ok = ph.ok && run_rowblock(st, p, nullptr, 1.0, trial_beta(), x, ph.y, false); // (builds and tunes the row-block side)
         // (round 5: the two kernels take turns over ranking_rounds() rounds and the medians decide, with a margin of 1.5 % for the named kernel --
         // until then one block of samples each and 3 %, which left `flat` 1-3 % behind `adaptive` on stand-ins where the row blocks are faster by
         // just that: the driver's round-4 run counted flat >= 0.70 on 7 and adaptive on 6 of the same 12 matrices.  A caller who wants the tile
         // kernel whatever it costs says so: tunable strict_strategy, or flat_rowblock 0)
-        ok = ok && timer.time_in_turns(st, 2, [&](int c) {
-          if (c == 0) launch_flat_with(st, p, policy_for(p, kFamFlat), 1.0, trial_beta(), x, scratch);
-          else (void)run_rowblock(st, p, nullptr, 1.0, trial_beta(), x, scratch, false);
+        ok = ok && ph.in_turns(2, [&](int c) {
+          if (c == 0) launch_flat_with(st, p, policy_for(p, kFamFlat), 1.0, trial_beta(), x, ph.y);
+          else (void)run_rowblock(st, p, nullptr, 1.0, trial_beta(), x, ph.y, false);
         }, ranking_rounds(), ms2);
         if (!ok) return false;
         const float ms_flat = ms2[0], ms_rb = ms2[1];
@@ -276,12 +271,8 @@ bool run_rowblock(hipStream_t st, Plan &p, const int *h_rowptr, double alpha, do
     if (v2[0] == v2[1] && r2[0] == r2[1]) {
       p.rb_target = cand[0]; // (short rows: both targets ask for more rows than a workgroup has lanes -- one shape)
     } else {
-      ++t_plan_work;
-      double *scratch = nullptr;
-      if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-      TuneTimer timer;
-      timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-      bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+      TimingPhase ph(st, p.A.m);
+      bool ok = ph.ok;
       bool skip[2] = {false, false};
       // (a candidate whose blocks the balance probe refuses is out; the probe and the digest are per shape: rebuilt per turn, plan time only)
       float ms[2] = {1e30f, 1e30f};
@@ -301,9 +292,9 @@ bool run_rowblock(hipStream_t st, Plan &p, const int *h_rowptr, double alpha, do
           rpb = r2[c];
           ok = setup();
           float t = 0.f;
-          ok = ok && timer.time(st, [&] {
+          ok = ok && ph.time([&] {
             const int zz = next_reverse(p) ? 64 : 0;
-            launch_rowblock_stream(st, p.A, vec, rpb, base_flags | (pol << 4) | zz, 1.0, trial_beta(), x, scratch, dg, cache_ends);
+            launch_rowblock_stream(st, p.A, vec, rpb, base_flags | (pol << 4) | zz, 1.0, trial_beta(), x, ph.y, dg, cache_ends);
           }, &t);
           if (ok && t < ms[c]) ms[c] = t; // (the smaller of the rounds: the candidates alternate, each turn a median of several launches)
         }
@@ -364,11 +355,8 @@ bool run_plus_prepare(Plan &p, const int *h_rowptr, hipStream_t st, const double
     return ensure_plus(p, h_rowptr, st, p.rowblock_ok == 0 ? kPlusMinNnz : 1536) && autotune_policy(p, kFamPlus, st, launch);
   // first call on this matrix: cache policy on the middle candidate, then the three block sizes under that policy
   if (!ensure_plus(p, h_rowptr, st, 1536) || !autotune_policy(p, kFamPlus, st, launch)) return false;
-  double *scratch = nullptr;
-  if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-  TuneTimer timer;
-  timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-  bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+  TimingPhase ph(st, p.A.m);
+  bool ok = ph.ok;
   const int candidates[3] = {1536, 1920, kPlusMinNnz};
   float best = 1e30f;
   int best_min = kPlusMinNnz;
@@ -376,7 +364,7 @@ bool run_plus_prepare(Plan &p, const int *h_rowptr, hipStream_t st, const double
     ok = ensure_plus(p, h_rowptr, st, candidates[c]);
     if (!ok) break;
     float ms = 0.f;
-    ok = timer.time(st, [&] { launch(policy_for(p, kFamPlus), scratch); }, &ms);
+    ok = ph.time([&] { launch(policy_for(p, kFamPlus), ph.y); }, &ms);
     if (ok) tune_log("m %d nnz %d beta class %d row-block-plus: MIN_NNZ_PER_BLOCK %d -> %.2f us (kept for both classes)", p.A.m, p.A.nnz, t_beta_class, candidates[c], ms * 1e3f);
     if (ok && ms < best) {
       best = ms;
@@ -403,15 +391,12 @@ static bool decide_whole_pass_hint(hipStream_t st, Plan &p, const double *x) {
   if (p.hint_state < 0 && !t_capturing && !ensure_hint(p, st)) return false;
   if (p.hint_state != 1 || !p.d_cold) return true;
   if (p.seg_whole_hint >= 0 || t_capturing || by_rule()) return true;
-  double *scratch = nullptr;
-  if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-  ++t_plan_work;
-  TuneTimer timer; // (no y reset: the pass adds into whatever the scratch holds)
+  TimingPhase ph(st, p.A.m, /*reset_y=*/false); // (no y reset: the pass adds into whatever the scratch holds)
   float ms[2] = {0.f, 0.f};
-  bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+  bool ok = ph.ok;
   for (int h = 0; ok && h < 2; ++h)
-    ok = timer.time(st, [&] {
-      launch_segment_tiles(st, p.seg_blocks[s], 1.0, p.seg_blk[s], p.seg_row[s], p.seg_begin[s], p.seg_vptr[s], p.A.ci, p.A.v, x, p.d_seg_ys, scratch,
+    ok = ph.time([&] {
+      launch_segment_tiles(st, p.seg_blocks[s], 1.0, p.seg_blk[s], p.seg_row[s], p.seg_begin[s], p.seg_vptr[s], p.A.ci, p.A.v, x, p.d_seg_ys, ph.y,
                            h ? p.d_cold : nullptr);
     }, &ms[h]);
   if (!ok) return false;
@@ -473,29 +458,19 @@ bool run_plus(hipStream_t st, Plan &p, const int *h_rowptr, double alpha, double
       }
     }
     if (p.seg_state != 1) return true;
-    ++t_plan_work;
-    double *scratch = nullptr;
-    if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-    TuneTimer timer;
-    timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-    bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
-    const double *keep_yin = p.A.yin;
-    p.A.yin = nullptr; // (the trial runs update the scratch vector in place)
-    ok = ok && decide_whole_pass_hint(st, p, x); // (the passes' own choice first, outside the clock of the comparison)
-    t_in_segment_timing = true;
+    TimingPhase ph(st, p.A.m);
+    ScopedSet<const double *> no_yin(p.A.yin, nullptr); // (the trial runs update the scratch vector in place)
+    bool ok = ph.ok && decide_whole_pass_hint(st, p, x); // (the passes' own choice first, outside the clock of the comparison)
+    ScopedSet in_timing(t_in_segment_timing, true);
     // (launches of >= 4 ms are sampled once each; a decision that is kept for the life of the plan gets a second sample of both -- the smaller
     // counts -- only where the first ones are within a third of each other: on R-MAT 25, 8.5 ms against 5.0, the second pair was 13 ms of a
     // 97 ms first call and could not have changed anything)
-    ok = ok && timer.time(st, [&] { launch_here(1.0, trial_beta(), scratch); }, &ms[0]) &&
-         timer.time(st, [&] { run_segments(st, p, 1.0, trial_beta(), x, scratch); }, &ms[1]);
+    ok = ok && ph.time([&] { launch_here(1.0, trial_beta(), ph.y); }, &ms[0]) && ph.time([&] { run_segments(st, p, 1.0, trial_beta(), x, ph.y); }, &ms[1]);
     if (ok && ms[0] < 1.33f * ms[1] && ms[1] < 1.33f * ms[0]) {
       float again[2] = {0.f, 0.f};
-      ok = timer.time(st, [&] { launch_here(1.0, trial_beta(), scratch); }, &again[0]) &&
-           timer.time(st, [&] { run_segments(st, p, 1.0, trial_beta(), x, scratch); }, &again[1]);
+      ok = ph.time([&] { launch_here(1.0, trial_beta(), ph.y); }, &again[0]) && ph.time([&] { run_segments(st, p, 1.0, trial_beta(), x, ph.y); }, &again[1]);
       if (ok) ms[0] = std::min(ms[0], again[0]), ms[1] = std::min(ms[1], again[1]);
     }
-    t_in_segment_timing = false;
-    p.A.yin = keep_yin;
     *timed = ok;
     return ok;
   };
@@ -510,12 +485,10 @@ bool run_plus(hipStream_t st, Plan &p, const int *h_rowptr, double alpha, double
     if (!ensure_hint(p, st)) return false;
     p.seg_early_tried = true; // (once per plan: an undecided outcome leaves the question to the comparison against the TUNED kernel below)
     if (p.hint_state == 1) {
-      const bool was_coarse = t_coarse_tuning;
-      t_coarse_tuning = t_no_policy_timing = true;
-      const bool prepared = run_plus_prepare(p, h_rowptr, st, x);
-      t_coarse_tuning = was_coarse;
-      t_no_policy_timing = false;
-      if (!prepared) return false;
+      {
+        ScopedSet coarse(t_coarse_tuning, true), no_policy(t_no_policy_timing, true);
+        if (!run_plus_prepare(p, h_rowptr, st, x)) return false;
+      }
       float ms[2] = {0.f, 0.f};
       bool timed = false;
       if (!time_against_segments(ms, &timed)) return false;
@@ -602,17 +575,13 @@ bool run_adaptive_timed(hipStream_t st, Plan &p, const int *h_rowptr, double alp
   float *ms = p.adaptive_ms[cls];
   const bool open = p.adaptive_family[cls] < 0 || p.adaptive_provisional[cls];
   if (open && !t_capturing && !(p.adaptive_family[cls] >= 0 && defer_tuning())) {
-    ++t_plan_work;
-    double *scratch = nullptr;
-    if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-    TuneTimer timer;
-    timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-    bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+    TimingPhase ph(st, p.A.m);
+    bool ok = ph.ok;
     // The families are compared in the caller's beta class: with beta != 0 every row also reads its old y, which is a large
     // share of the traffic where rows hold one or two non-zeros and ranks the families differently (15 M rows of ~1 nnz:
     // flat looked 3 % faster than the row blocks at beta = 0 and is 9 % slower at beta = 1).
     const double beta_trial = trial_beta();
-    t_coarse_tuning = true;
+    ScopedSet coarse(t_coarse_tuning, true);
     bool any_measured = false;
     int timed_here = 0;
     for (int f = 0; f < 3; ++f) any_measured = any_measured || ms[f] < 1e29f;
@@ -626,13 +595,13 @@ bool run_adaptive_timed(hipStream_t st, Plan &p, const int *h_rowptr, double alp
         t_tuning_deferred = true;
         break;
       }
-      ok = run_family(f, 1.0, beta_trial, scratch); // builds this family's plan (sub-choices at their defaults)
+      ok = run_family(f, 1.0, beta_trial, ph.y); // builds this family's plan (sub-choices at their defaults)
       if (!ok) break;
       if (f == 0 && p.rowblock_ok == 0) { // fixed row blocks were rescued: that run WAS family 1
         p.adaptive_skipped[cls][0] = true;
         continue;
       }
-      ok = timer.time(st, [&] { (void)run_family(f, 1.0, beta_trial, scratch); }, &ms[f]);
+      ok = ph.time([&] { (void)run_family(f, 1.0, beta_trial, ph.y); }, &ms[f]);
       any_measured = any_measured || ok;
       ++timed_here;
     }
@@ -652,13 +621,12 @@ bool run_adaptive_timed(hipStream_t st, Plan &p, const int *h_rowptr, double alp
       for (int f = 0; f < 3; ++f) close += (skip[f] = ms[f] > 1.08f * fastest) ? 0 : 1;
       if (close > 1) {
         float again[3] = {1e30f, 1e30f, 1e30f};
-        ok = timer.time_in_turns(st, 3, [&](int f) { (void)run_family(f, 1.0, beta_trial, scratch); }, ranking_rounds(), again, skip);
+        ok = ph.in_turns(3, [&](int f) { (void)run_family(f, 1.0, beta_trial, ph.y); }, ranking_rounds(), again, skip);
         for (int f = 0; ok && f < 3; ++f)
           if (!skip[f]) ms[f] = ranking_rounds() > 1 ? again[f] : (again[f] < ms[f] ? again[f] : ms[f]);
       }
       looked_twice = ok;
     }
-    t_coarse_tuning = false;
     const int best_family = decide(ms, looked_twice && ranking_rounds() > 1);
     tune_log("m %d nnz %d adaptive (beta %s 0): fixed row blocks %.2f us, row-block-plus %.2f us, flat %.2f us -> family %d%s", p.A.m, p.A.nnz,
              beta != 0.0 ? "!=" : "==", ms[0] * 1e3f, ms[1] * 1e3f, ms[2] * 1e3f, best_family,
@@ -705,8 +673,7 @@ static bool run_col_slabs(Plan &p, int S, int strategy, hipStream_t st, double a
   // y = beta * y_in first (nothing to do for beta == 1 in place), then every slab: y_s = alpha * A_s x over the slab's non-empty
   // rows (an ordinary SpMV of a smaller matrix, beta = 0) and y[rowid] += y_s
   if (beta != 1.0 || p.A.yin) launch_scale_y(st, m, beta, dy, p.A.yin);
-  const bool outer = !t_in_slab;
-  t_in_slab = true;
+  ScopedSet in_slab(t_in_slab, true);
   for (int s = 0; s < S && last_error_code_only() == kOk; ++s) {
     const long long o = p.slab_off[s];
     const int ms = p.slab_rows[s];
@@ -715,7 +682,6 @@ static bool run_col_slabs(Plan &p, int S, int strategy, hipStream_t st, double a
              p.d_slab_ys, nullptr);
     if (last_error_code_only() == kOk) launch_slab_merge(st, ms, p.slab_rowid[s], p.d_slab_ys, dy);
   }
-  if (outer) t_in_slab = false;
   p.last_kernel = kKernelColSlabs;
   return last_error_code_only() == kOk;
 }
@@ -747,40 +713,29 @@ static int slab_copy_auto(Plan &p, int strategy, hipStream_t st, int n, const do
       tune_log("m %d nnz %d: slab-major copy not built: %.1f GB free, 3 x 12 B per non-zero = %.1f GB wanted", p.A.m, p.A.nnz, free_b / 1e9, 36e-9 * p.A.count());
       return 0;
     }
-    ++t_plan_work;
     const int count = p.A.count() < kValueSamples ? p.A.count() : kValueSamples;
-    bool ok = ensure_slabs(p, S, st) &&
+    TimingPhase ph(st, p.A.m);
+    bool ok = ph.ok && ensure_slabs(p, S, st) &&
               hip_ok(hipMalloc(reinterpret_cast<void **>(&p.d_value_samples), 12 * static_cast<size_t>(count) + 8), "hipMalloc value samples") &&
               hip_ok(hipHostMalloc(reinterpret_cast<void **>(&p.h_values_changed), sizeof(int)), "hipHostMalloc value flag");
-    double *scratch = ok ? tune_scratch(static_cast<size_t>(p.A.m)) : nullptr;
-    ok = ok && scratch != nullptr;
     if (ok) {
       *p.h_values_changed = 0;
       p.value_samples = count;
       launch_value_samples(st, p.A.v, p.A.ci, p.A.nnz0, p.A.count() - 1, count, p.d_value_samples, nullptr);
-      ok = hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
       // the slabs' own plans settle first (every slab is an ordinary matrix with its own timed choices), outside any budget
-      struct Unbounded {
-        Unbounded() { ++t_unbounded_tuning; }
-        ~Unbounded() { --t_unbounded_tuning; }
-      } unbounded;
-      const double saved_budget = t_budget_spmvs;
-      t_budget_spmvs = 0.0;
+      UnboundedTuningScope unbounded;
+      ScopedSet no_budget(t_budget_spmvs, 0.0);
       for (int round = 0; ok && round < 4 && !adopted; ++round) {
         const unsigned w0 = t_plan_work;
-        ok = run_col_slabs(p, S, strategy, st, 1.0, trial_beta(), p.A.m, n, dx, scratch) && hip_ok(hipStreamSynchronize(st), "settle the slabs' plans");
+        ok = run_col_slabs(p, S, strategy, st, 1.0, trial_beta(), p.A.m, n, dx, ph.y) && hip_ok(hipStreamSynchronize(st), "settle the slabs' plans");
         if (t_plan_work == w0) break;
       }
-      TuneTimer timer;
-      timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
       float ms[2] = {0.f, 0.f};
-      t_in_segment_timing = true;
-      ok = ok && timer.ok && (adopted || timer.time_in_turns(st, 2, [&](int c) {
-        if (c == 0) run_segments(st, p, 1.0, trial_beta(), dx, scratch);
-        else (void)run_col_slabs(p, S, strategy, st, 1.0, trial_beta(), p.A.m, n, dx, scratch);
+      ScopedSet in_timing(t_in_segment_timing, true);
+      ok = ok && (adopted || ph.in_turns(2, [&](int c) {
+        if (c == 0) run_segments(st, p, 1.0, trial_beta(), dx, ph.y);
+        else (void)run_col_slabs(p, S, strategy, st, 1.0, trial_beta(), p.A.m, n, dx, ph.y);
       }, 2, ms));
-      t_in_segment_timing = false;
-      t_budget_spmvs = saved_budget;
       if (ok && !adopted) {
         p.slab_copy_choice = (ms[1] < 0.97f * ms[0] || tun(kT_col_slabs) == -2) ? 1 : 0; // (-2: tests keep the copy whatever the timing says)
         tune_log("m %d nnz %d: slab passes over run lists %.1f us, slab-major copy (%d slabs, %.2f GB held) %.1f us -> %s", p.A.m, p.A.nnz, ms[0] * 1e3f, S,
@@ -843,12 +798,7 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
   // (a forced slab-major copy -- col_slabs >= 2 -- is pinned by the caller and holds the matrix a second time: no twin of that)
   bool early = rule_until_settled() && !t_in_slab && !t_rule_twin && t_unbounded_tuning == 0 && m > 0 && d_rowptr && dy && strategy >= 0 &&
                strategy < kStrategyCount && strategy < 32 && tun(kT_col_slabs) < 2;
-  bool capturing = false;
-  if (early) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    capturing = hipStreamIsCapturing(t_stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-  }
+  const bool capturing = early && stream_capturing(t_stream);
   if (early) early = !plan_settled_for(d_rowptr, d_colindex, d_value, m, n, strategy, beta != 0.0 ? 1 : 0);
   if (!early) {
     run_spmv_call(strategy, trans, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dx, dy, dy_in);
@@ -863,10 +813,7 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
   if (capturing) {
     // a capture of an unsettled plan records what serves such a plan: the twin's kernels (nothing is timed inside a capture) -- and the twin stays
     // alive for the graph's sake when the plan settles later
-    struct TwinScope {
-      TwinScope() { t_rule_twin = true; }
-      ~TwinScope() { t_rule_twin = false; }
-    } twin;
+    ScopedSet twin(t_rule_twin, true);
     run_spmv_call(strategy, trans, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dx, dy, dy_in);
     return;
   }
@@ -875,10 +822,7 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
   // 1. the caller's y, by rule
   int served_kernel = -1, served_c16 = 0;
   {
-    struct TwinScope {
-      TwinScope() { t_rule_twin = true; }
-      ~TwinScope() { t_rule_twin = false; }
-    } twin;
+    ScopedSet twin(t_rule_twin, true);
     run_spmv_call(strategy, trans, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dx, dy, dy_in);
     if (const std::shared_ptr<Plan> tp = t_last_plan.lock()) {
       served_kernel = tp->last_kernel;
@@ -895,9 +839,10 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
   }
   (void)hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(m), t_stream);
   t_early_began = began;
-  t_early_clock = true;
-  run_spmv_call(strategy, 0, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dx, scratch, nullptr);
-  t_early_clock = false;
+  {
+    ScopedSet early_clock(t_early_clock, true);
+    run_spmv_call(strategy, 0, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dx, scratch, nullptr);
+  }
   t_last_prepare_us += twin_prepare_us;
   // 3. what the caller can ask about is the plan being settled, served so far by its twin's kernel
   if (const std::shared_ptr<Plan> p = t_last_plan.lock()) {
@@ -943,11 +888,7 @@ void run_spmv_call(int strategy, int trans, double alpha, double beta, int m, in
   }
   hipStream_t st = t_stream;
   note_stream_use();
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    t_capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-  }
+  t_capturing = stream_capturing(st);
   if (strategy < 0 || strategy >= kStrategyCount) {
     set_error(kErrUnknownStrategy, "unknown strategy id");
     return;
@@ -1030,11 +971,7 @@ void run_spmv_call(int strategy, int trans, double alpha, double beta, int m, in
     return;
   }
   // tunable strict_strategy: the name the caller gave binds the kernel (run_flat, run_plus); a slab of the opt-in column slabs keeps its parent's
-  struct StrictScope {
-    int prev;
-    ~StrictScope() { t_strict_name = prev; }
-  } strict_scope{t_strict_name};
-  if (!t_in_slab) t_strict_name = tun(kT_strict_strategy) ? strategy : -1;
+  ScopedSet strict_scope(t_strict_name, t_in_slab ? t_strict_name : (tun(kT_strict_strategy) ? strategy : -1));
   if (!d_colindex || !d_value) {
     set_error(kErrBadArgument, "null colindex / value with nnz > 0");
     return;

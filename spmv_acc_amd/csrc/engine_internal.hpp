@@ -1,6 +1,7 @@
-// engine_internal.hpp -- what the four translation units of the engine share (config.cpp, plan.cpp, tuner.cpp, dispatch.cpp): the Plan, the
-// tunables' ids, the per-call thread-local state, the timing helper and the two timing templates.  Not installed, not part of any API:
-// everything here lives in spmv_acc::detail.  (Round 4: engine.cpp, 2,900 lines in one file, was split along these lines; no behaviour change.)
+// engine_internal.hpp -- what the translation units of the engine share (config.cpp, plan.cpp, tuner.cpp, dispatch.cpp, spmm.cpp): the Plan, the
+// tunables' ids, the per-call thread-local state and ScopedSet (which sets a piece of it for a scope), the capture query, the timer (TuneTimer), the
+// opening every per-matrix timing phase shares (TimingPhase) and the three timing templates (cache policy, gather hints, 16-bit columns).  Not
+// installed, not part of any API: everything here lives in spmv_acc::detail.  (Round 4: engine.cpp, 2,900 lines in one file, was split along these lines.)
 #pragma once
 
 #include "engine.hpp"
@@ -39,6 +40,22 @@ int last_error_code_only();
 extern thread_local double t_last_prepare_us;
 extern thread_local unsigned t_plan_work; // bumped by every once-per-matrix step (structural pass, probe, timing) that really runs
 extern const char *const kStaleText;
+// is a stream capture recording on st?  (the query's own error, if any, is not left behind as the thread's last HIP error)
+inline bool stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  return capturing;
+}
+// Sets `ref` to `value` for the life of the scope and puts the old value back on every way out (the per-call thread-local flags).
+template <typename T> struct ScopedSet {
+  T &ref;
+  const T old;
+  ScopedSet(T &r, T value) : ref(r), old(r) { ref = value; }
+  ~ScopedSet() { ref = old; }
+  ScopedSet(const ScopedSet &) = delete;
+  ScopedSet &operator=(const ScopedSet &) = delete;
+};
 struct Tunable {
   const char *name;
   int def;
@@ -360,6 +377,12 @@ struct TuneTimer {
   static constexpr int kMaxTimed = 5;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipEvent_t per[2 * kMaxTimed] = {};
+  // The trial launches write a scratch y.  With a reset buffer set (TimingPhase) the timed launches
+  // follow the REFERENCE HARNESS'S protocol -- the one every figure of this repository is quoted on (benchmark/csr_spmv.hpp:66-74):
+  // the scratch y is rewritten before each launch, each launch has its own event pair, the median counts -- instead of one event
+  // pair around back-to-back launches.  Back-to-back timing favours whatever profits most from the previous launch's cache
+  // contents and hides a second kernel's launch gap; candidates a few per cent apart ranked differently under the two protocols
+  // (af_shell10-sized: adaptive kept fixed row blocks, 121.6 us per launch with y reset, where flat runs 118.2).
   void *reset_ptr = nullptr;
   size_t reset_bytes = 0;
   bool ok = false;
@@ -372,16 +395,6 @@ struct TuneTimer {
     if (e1) (void)hipEventDestroy(e1);
     for (auto &e : per)
       if (e) (void)hipEventDestroy(e);
-  }
-  // The trial launches write a scratch y.  With a reset buffer set the timed launches
-  // follow the REFERENCE HARNESS'S protocol -- the one every figure of this repository is quoted on (benchmark/csr_spmv.hpp:66-74):
-  // the scratch y is rewritten before each launch, each launch has its own event pair, the median counts -- instead of one event
-  // pair around back-to-back launches.  Back-to-back timing favours whatever profits most from the previous launch's cache
-  // contents and hides a second kernel's launch gap; candidates a few per cent apart ranked differently under the two protocols
-  // (af_shell10-sized: adaptive kept fixed row blocks, 121.6 us per launch with y reset, where flat runs 118.2).
-  void set_reset(void *ptr, size_t bytes) {
-    reset_ptr = ptr;
-    reset_bytes = bytes;
   }
   // at_least: launches a decision kept for the life of the plan rests on, whatever they cost (a launch of >= 4 ms is otherwise timed once)
   template <typename F> bool time(hipStream_t st, F &&fn, float *ms_per_launch, int at_least = 1) {
@@ -469,6 +482,30 @@ struct TuneTimer {
 // rounds of a ranking between near-equal candidates: three where the call may spend (spmv_acc_prepare), one under a call's tuning budget
 inline int ranking_rounds() { return t_budget_spmvs > 0.0 ? 1 : 3; }
 
+// What every per-matrix timing phase opens with: the phase counts as plan work, takes the call's shared scratch y (tune_scratch) zeroed on the
+// stream -- in the beta != 0 class the trial launches accumulate into it -- and times on it with a TuneTimer that rewrites it before each timed
+// launch (reset_y = false: the launches add into whatever it holds).  ok: scratch, events and memset are all there.  Each phase keeps its own
+// candidates, sampling, margin and decision; time() and in_turns() are TuneTimer::time and time_in_turns on the phase's stream.
+struct TimingPhase {
+  hipStream_t st;
+  double *y;
+  TuneTimer timer;
+  bool ok;
+  TimingPhase(hipStream_t stream, int m, bool reset_y = true) : st(stream), y(tune_scratch(static_cast<size_t>(m))) {
+    ++t_plan_work;
+    const size_t bytes = sizeof(double) * static_cast<size_t>(m);
+    if (reset_y) {
+      timer.reset_ptr = y;
+      timer.reset_bytes = bytes;
+    }
+    ok = y && timer.ok && hip_ok(hipMemsetAsync(y, 0, bytes, st), "memset tune y");
+  }
+  template <typename F> bool time(F &&fn, float *ms, int at_least = 1) { return timer.time(st, fn, ms, at_least); }
+  template <typename F> bool in_turns(int n, F &&launch, int rounds, float *ms, const bool *skip = nullptr) {
+    return timer.time_in_turns(st, n, launch, rounds, ms, skip);
+  }
+};
+
 // Time the stream-load cache policies on THIS matrix with the kernel family that will run it (scratch y, beta = 0:
 // no side effects on the caller's y) and keep the fastest.  Up to eight launches per candidate (TuneTimer: 3 to reach
 // that policy's cache steady state + 5 timed; 2 in all when a launch takes milliseconds), once per matrix.
@@ -479,9 +516,7 @@ template <typename Launch> bool autotune_policy(Plan &p, int fam, hipStream_t st
   // A matrix prepared in one beta class (spmv_acc_prepare: beta = 1) and then CAPTURED into a hipGraph in the other: timing would
   // synchronise inside the capture.  The call runs under the policy the other class measured (policy_for's fallback) and this
   // class is timed by the first call made outside a capture.
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone) return true;
-  (void)hipGetLastError();
+  if (stream_capturing(st)) return true;
   // While adaptive compares the families only the first one times the three policies; the others run under that result
   // (policy_for) and the family that wins times its own on its next call.  (Timing all three per family made adaptive's
   // first call 21 ms on the Hardesty3-sized matrix, 134 SpMVs' worth; the comparison itself needs 8 launches per family.)
@@ -489,13 +524,8 @@ template <typename Launch> bool autotune_policy(Plan &p, int fam, hipStream_t st
     for (int f = 0; f < kFamilyCount; ++f)
       if (p.stream_policy[f][cls] >= 0) return true;
   }
-  ++t_plan_work;
-  double *scratch = nullptr;
-  if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-  TuneTimer timer;
-  timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-  // (zeroed: in the beta != 0 class the trial launches accumulate into it)
-  bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+  TimingPhase ph(st, p.A.m);
+  bool ok = ph.ok;
   const int candidates[3] = {kStreamPolicyNt, kStreamPolicyDefault, kStreamPolicyValueDefault};
   float best = 1e30f;
   int best_policy = kStreamPolicyNt;
@@ -503,7 +533,7 @@ template <typename Launch> bool autotune_policy(Plan &p, int fam, hipStream_t st
     // the policies differ through what they leave in the Infinity Cache for the NEXT SpMV, so each candidate first
     // runs until the caches hold its own steady state, then is timed over several launches
     float ms = 0.f;
-    ok = timer.time(st, [&] { launch(candidates[c], scratch); }, &ms);
+    ok = ph.time([&] { launch(candidates[c], ph.y); }, &ms);
     if (ok) tune_log("m %d nnz %d family %d beta class %d: stream policy %d -> %.2f us", p.A.m, p.A.nnz, fam, cls, candidates[c], ms * 1e3f);
     if (ok && ms < best) {
       best = ms;
@@ -521,10 +551,7 @@ template <class Launch> bool autotune_hint(Plan &p, int fam, hipStream_t st, Lau
   p.A.cold = nullptr;
   const int mode = tun(kT_gather_hint);
   if (mode == 0) return true;
-  if (p.hint_state < 0 || (mode < 0 && p.hint_state == 1 && p.hint_use[fam] < 0)) { // census / timing ahead: not inside a capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return true;
-  }
+  if ((p.hint_state < 0 || (mode < 0 && p.hint_state == 1 && p.hint_use[fam] < 0)) && stream_capturing(st)) return true; // census / timing ahead: not inside a capture
   if (!ensure_hint(p, st)) return false;
   if (p.hint_state != 1) return true;
   if (mode > 0 || tun(kT_deterministic)) { // forced / by rule: wherever the census found a hot set worth protecting
@@ -533,16 +560,12 @@ template <class Launch> bool autotune_hint(Plan &p, int fam, hipStream_t st, Lau
   }
   if (p.hint_use[fam] < 0 && defer_tuning()) return true; // (plain gathers for now; timed by a later call)
   if (p.hint_use[fam] < 0) {
-    ++t_plan_work;
-    double *scratch = nullptr;
-    if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-    TuneTimer timer;
-    timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-    bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+    TimingPhase ph(st, p.A.m);
+    bool ok = ph.ok;
     float ms[2] = {0.f, 0.f};
     for (int h = 0; ok && h < 2; ++h) {
       p.A.cold = h ? p.d_cold : nullptr;
-      ok = timer.time(st, [&] { launch(scratch); }, &ms[h]);
+      ok = ph.time([&] { launch(ph.y); }, &ms[h]);
     }
     p.A.cold = nullptr;
     if (!ok) return false;
@@ -566,23 +589,14 @@ template <class Launch> bool autotune_col16(Plan &p, int fam, hipStream_t st, La
   if (mode < 0 && (tun(kT_deterministic) || p.c16_use[fam] == 0)) return true;
   const bool undecided = p.col16.state < 0 || (mode < 0 && p.c16_use[fam] < 0);
   if (undecided) {
-    if (t_capturing || (mode < 0 && (t_coarse_tuning || t_no_policy_timing || defer_tuning()))) return true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return true;
-    (void)hipGetLastError();
+    if (t_capturing || (mode < 0 && (t_coarse_tuning || t_no_policy_timing || defer_tuning())) || stream_capturing(st)) return true;
   }
   if (!ensure_col16(p, st)) return false;
   if (p.col16.state != 1) return true;
   if (mode < 0 && p.c16_use[fam] < 0) {
-    ++t_plan_work;
-    double *scratch = nullptr;
-    if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-    TuneTimer timer;
-    timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-    bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+    TimingPhase ph(st, p.A.m);
     float ms[2] = {0.f, 0.f};
-    ok = ok && timer.time_in_turns(st, 2, [&](int c) { launch(c ? &p.col16 : nullptr, scratch); }, ranking_rounds(), ms);
-    if (!ok) return false;
+    if (!ph.ok || !ph.in_turns(2, [&](int c) { launch(c ? &p.col16 : nullptr, ph.y); }, ranking_rounds(), ms)) return false;
     p.c16_use[fam] = ms[1] < 0.985f * ms[0] ? 1 : 0;
     tune_log("m %d nnz %d family %d beta class %d 16-bit columns (%d ints per chunk record, %lld escapes, %lld in overflow): colindex %.2f us, encoding %.2f us -> %s",
              p.A.m, p.A.nnz, fam, t_beta_class, p.col16.rec_ints, p.col16.escapes, p.col16.overflow, ms[0] * 1e3f, ms[1] * 1e3f,

@@ -96,11 +96,7 @@ int run_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz
   }
   hipStream_t st = t_stream;
   note_stream_use();
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    t_capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-  }
+  t_capturing = stream_capturing(st);
   if (nnz == 0 || n == 0) {
     launch_spmm_scale(st, m, k, row_major, ldy, beta, dY);
   } else {

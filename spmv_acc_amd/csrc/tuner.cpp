@@ -434,16 +434,12 @@ bool autotune_flat_mode(Plan &p, hipStream_t st, const double *x) {
     F.needs_fixup = true;
     return true;
   }
-  ++t_plan_work;
-  double *scratch = nullptr;
-  if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-  TuneTimer timer;
-  timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-  bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+  TimingPhase ph(st, p.A.m);
+  bool ok = ph.ok;
   float ms[2] = {0.f, 0.f};
   for (int mode = 0; ok && mode < 2; ++mode) {
     F.needs_fixup = mode == 0;
-    ok = timer.time(st, [&] { launch_flat_with(st, p, policy_for(p, kFamFlat), 1.0, trial_beta(), x, scratch); }, &ms[mode]);
+    ok = ph.time([&] { launch_flat_with(st, p, policy_for(p, kFamFlat), 1.0, trial_beta(), x, ph.y); }, &ms[mode]);
   }
   F.tuned_fixup[cls] = F.needs_fixup = !(ok && ms[1] < ms[0]);
   F.mode_tuned[cls] = ok;
@@ -463,12 +459,8 @@ bool autotune_flat_geometry(Plan &p, hipStream_t st, const double *x) {
   }
   const bool time_npt = tun(kT_flat_npt) < 0, time_early = tun(kT_flat_early) < 0;
   if (!time_npt && !time_early) return true; // pinned (A/B runs)
-  ++t_plan_work;
-  double *scratch = nullptr;
-  if (!(scratch = tune_scratch(static_cast<size_t>(p.A.m)))) return false;
-  TuneTimer timer;
-  timer.set_reset(scratch, sizeof(double) * static_cast<size_t>(p.A.m));
-  bool ok = timer.ok && hip_ok(hipMemsetAsync(scratch, 0, sizeof(double) * static_cast<size_t>(p.A.m), st), "memset tune y");
+  TimingPhase ph(st, p.A.m);
+  bool ok = ph.ok;
   const int pol = policy_for(p, kFamFlat);
   FlatPlan alt;
   FlatPlan *plans[2] = {&p.flat, nullptr};
@@ -489,7 +481,7 @@ bool autotune_flat_geometry(Plan &p, hipStream_t st, const double *x) {
     for (int e = 0; ok && e < (time_early ? 2 : 1); ++e) {
       plans[k]->early_stream = time_early ? e != 0 : plans[k]->early_stream;
       float ms = 0.f;
-      ok = timer.time(st, [&] { launch_flat_plan(st, p.A, *plans[k], pol, 1.0, trial_beta(), x, scratch, next_reverse(p)); }, &ms);
+      ok = ph.time([&] { launch_flat_plan(st, p.A, *plans[k], pol, 1.0, trial_beta(), x, ph.y, next_reverse(p)); }, &ms);
       if (ok) tune_log("m %d nnz %d flat geometry: %d non-zeros per tile, stream-first %d -> %.2f us", p.A.m, p.A.nnz, plans[k]->stride,
                        plans[k]->early_stream ? 1 : 0, ms * 1e3f);
       if (ok && ms < best) {
