@@ -313,6 +313,10 @@ int spmv_acc_query_plan_settled(const int *d_rowptr, int m);
  * place (same rowptr) call spmv_acc_release_plans (64 samples of colindex are re-checked by every launch, like rowptr's).  No reference counterpart:
  * the reference streams one 4-byte column per non-zero (hip-flat/flat_imp_one_pass.hpp:35-39, hip-line-enhance/line_enhance_spmv_imp.inl:55-62). */
 int spmv_acc_query_plan_col16(const int *d_rowptr, int m);
+/* The code width of that encoding (round 7): 16 or 8 bits per non-zero (8: where a chunk's near columns lie within 255 of each other -- the plan
+ * picks the width by rule from its escape statistics, tunable col16 = 8 / 2 pins 8- / 16-bit codes); 0 = the caller's colindex was streamed;
+ * -1 = no SpMV yet; -2 = no such plan. */
+int spmv_acc_query_plan_col_bits(const int *d_rowptr, int m);
 /* Which kernel ran the plan's LATEST SpMV (round 5).  The reference's strategy name IS its kernel (strategy_picker.cpp:19-65); here a name selects a
  * policy by default (`flat` may run the row-block kernel where it timed faster, `line_enhance` the column-slab passes on power-law columns) and
  * tunable strict_strategy = 1 (SPMV_ACC_TUNABLES=strict_strategy=1) binds the name to its algorithm.  -1 = no SpMV yet, -2 = no such plan. */

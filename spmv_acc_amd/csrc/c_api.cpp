@@ -399,6 +399,10 @@ int spmv_acc_query_plan_col16(const int *d_rowptr, int m) {
   PlanInfo info;
   return query_plan(d_rowptr, m, &info) ? info.col16 : -2;
 }
+int spmv_acc_query_plan_col_bits(const int *d_rowptr, int m) {
+  PlanInfo info;
+  return query_plan(d_rowptr, m, &info) ? info.col_bits : -2;
+}
 int spmv_acc_query_plan_settled(const int *d_rowptr, int m) {
   PlanInfo info;
   return query_plan(d_rowptr, m, &info) ? info.settled : -2;

@@ -121,7 +121,8 @@ Tunable g_tunables[] = {
                                // uneven matrices keep)
     {"col16", -1, -1},         // 16-bit column encoding (k_col16.hip; row blocks and flat): -1 = built once per plan and timed against the caller's
                                // colindex per kernel family, kept where it wins by > 1.5 %; 0 never; 1 always where it can be built (16 / 32 / 64
-                               // also pin the record size: tests).  A plan that uses it holds structure DERIVED from colindex: 64 samples of
+                               // also pin the record size: tests).  Its codes are 8 bits wide where the rule of tuner.cpp ensure_col16 allows (same
+                               // record size, <= 0.5 % of nnz more escapes), else 16; 8 / 2 = always, with 8- / 16-bit codes pinned (A/B runs, tests).  A plan that uses it holds structure DERIVED from colindex: 64 samples of
                                // colindex are re-checked by every launch (like rowptr's), an in-place edit between the samples needs
                                // spmv_acc_release_plans -- `deterministic` and col16 = 0 keep to the caller's arrays.
     {"vector_width", 0, 0},    // vector_row / light: lanes per row; 0 = the reference's rule (vector_row.cpp:15-27: pow2 >= avg row length / 2)

@@ -78,6 +78,7 @@ bool run_flat(hipStream_t st, Plan &p, double alpha, double beta, const double *
   launch_flat_with(st, p, policy_for(p, kFamFlat), alpha, beta, x, y);
   p.last_kernel = kKernelFlatTile;
   p.last_c16 = c16 && p.flat.stride == kThreads * kNnzPerThread && p.A.cold == nullptr ? c16->rec_ints : 0;
+  p.last_col_bits = p.last_c16 > 0 ? c16->bits : 0;
   return true;
 }
 
@@ -324,6 +325,7 @@ bool run_rowblock(hipStream_t st, Plan &p, const int *h_rowptr, double alpha, do
   launch_rowblock_stream(st, p.A, vec, rpb, base_flags | (policy_for(p, kFamRowblock) << 4) | zz, alpha, beta, x, y, dg, cache_ends, c16);
   p.last_kernel = kKernelRowblock;
   p.last_c16 = c16 && p.A.cold == nullptr ? c16->rec_ints : 0;
+  p.last_col_bits = p.last_c16 > 0 ? c16->bits : 0;
   return true;
 }
 
@@ -820,13 +822,14 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
   const auto began = std::chrono::steady_clock::now();
   const int err_before = last_error_code_only();
   // 1. the caller's y, by rule
-  int served_kernel = -1, served_c16 = 0;
+  int served_kernel = -1, served_c16 = 0, served_col_bits = 0;
   {
     ScopedSet twin(t_rule_twin, true);
     run_spmv_call(strategy, trans, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dx, dy, dy_in);
     if (const std::shared_ptr<Plan> tp = t_last_plan.lock()) {
       served_kernel = tp->last_kernel;
       served_c16 = tp->last_c16;
+      served_col_bits = tp->last_col_bits;
     }
   }
   if (last_error_code_only() != err_before && last_error_code_only() != kOk && last_error_code_only() != kErrUnsupportedTrans) return; // (the call failed: nothing to tune)
@@ -851,6 +854,7 @@ void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, 
     if (!((p->settled_for[cls] >> strategy) & 1u)) {
       p->last_kernel = served_kernel;
       p->last_c16 = served_c16;
+      p->last_col_bits = served_col_bits;
     }
   }
   if (plan_settled_for(d_rowptr, d_colindex, d_value, m, n, strategy, beta != 0.0 ? 1 : 0)) drop_rule_twin(d_rowptr, d_colindex, d_value, m, n);
@@ -964,6 +968,7 @@ void run_spmv_call(int strategy, int trans, double alpha, double beta, int m, in
   } yin_scope{p->A};
   p->A.yin = beta != 0.0 ? dy_in : nullptr;
   p->last_c16 = 0; // (run_rowblock / run_flat say otherwise when this call's kernel reads the 16-bit column encoding)
+  p->last_col_bits = 0;
 
   if (p->A.count() == 0) {
     launch_scale_y(st, m, beta, dy, p->A.yin);

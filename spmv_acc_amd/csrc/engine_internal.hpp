@@ -107,6 +107,7 @@ struct Plan {
   unsigned launches = 0;           // tile-kernel launches so far (parity = walking direction, tunable zigzag)
   double trial_ms = 0.0;           // a trial launch of this matrix as the per-matrix timings measured it: prices later calls' tuning budget
   int last_c16 = -1;               // the plan's latest SpMV read the 16-bit column encoding (its record ints) or colindex (0): spmv_acc_query_plan_col16
+  int last_col_bits = -1;          // ... with codes of this width (16 or 8), 0 = colindex: spmv_acc_query_plan_col_bits
   int last_kernel = -1;            // which kernel the plan's latest SpMV ran (kKernel*, below): spmv_acc_query_plan_last_kernel, strict_strategy's test
   bool tuning_open = true;         // some per-matrix timing was deferred (or has not been reached yet): later calls may resume it
   bool captured = false;           // a stream capture recorded kernels of this plan (a rule twin then outlives its plan's settling)
@@ -212,6 +213,7 @@ struct Plan {
   bool is_stale() const { return A.stale && __atomic_load_n(A.stale, __ATOMIC_RELAXED) != 0; }
   void free_col16() {
     if (col16.d16) (void)hipFree(col16.d16);
+    if (col16.d8) (void)hipFree(col16.d8);
     if (col16.rec) (void)hipFree(col16.rec);
     if (col16.ovf) (void)hipFree(col16.ovf);
     if (col16.ci_guard) (void)hipFree(col16.ci_guard);

@@ -17,6 +17,12 @@
 // r06_col16_counters.md).  With a fixed-stride record the record's address depends on nothing but the chunk index: it is requested
 // first, together with the stream, and only a chunk with more than E escapes pays a dependent load.
 // 4 B/nnz of column stream become 2 B + 4 R / 256 B (R = 16: 2.25 B/nnz).
+// 8-bit codes (round 7): the same records, a narrower window -- base = median - 127 (clamped at 0), d8[j] = colindex[j] - base if that fits in
+// [0, 254], 0xFF (escape) otherwise.  Where a chunk's near columns lie within 255 of each other (short rows drifting slowly: the Hardesty3-sized
+// matrix's 52 rows per chunk span ~65 columns) the escapes are the far columns either way and the stream is 1 B + 4 R / 256 B per non-zero.
+// Pass 1 counts the escapes of both widths; the host keeps 8-bit codes where their record size is the same and they add at most 0.5 % of
+// nnz in escapes (tuner.cpp ensure_col16).  The 8-bit window lies inside the 16-bit one (same median), so a chunk's 8-bit escapes include its
+// 16-bit ones.
 #include <climits>
 
 #include <rocprim/device/device_scan.hpp>
@@ -31,14 +37,49 @@ using namespace dev;
 
 constexpr int kChunk = kCol16Chunk;
 
-// One wavefront per chunk.  Pass 1: base + escape count; stats[0] += escapes, stats[1 .. 3] += chunks with more than 12 / 28 / 60 of them.
-__global__ __launch_bounds__(kThreads) void col16_base_kernel(const int *__restrict__ ci, int nnz, int chunk0, int nchunks,
-                                                              int *__restrict__ base, int *__restrict__ esc_count,
-                                                              unsigned long long *__restrict__ stats) {
+// the window of a code width: base = median - HALF (clamped at 0), codes 0 .. 2 HALF, 2 HALF + 1 = escape
+template <int BITS> struct CodeWidth;
+template <> struct CodeWidth<16> {
+  typedef unsigned short T;
+  static constexpr int half = 32767;
+};
+template <> struct CodeWidth<8> {
+  typedef unsigned char T;
+  static constexpr int half = 127;
+};
+
+// base and escape count of one chunk for one code width; lane 0 records them (stats, the workgroup's LDS tally: escapes, chunks above 12 / 28 / 60)
+template <int BITS>
+__device__ __forceinline__ void chunk_base(const int (&col)[4], int median, bool none, int lane, int c, int *__restrict__ base,
+                                           int *__restrict__ esc_count, unsigned long long *__restrict__ stats) {
+  constexpr int H = CodeWidth<BITS>::half;
+  long long b = static_cast<long long>(median) - H;
+  if (none || b < 0) b = 0;
+  const int bs = static_cast<int>(b);
+  int esc = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (col[e] != INT_MAX) {
+      const long long d = static_cast<long long>(col[e]) - bs;
+      esc += (d < 0 || d > 2 * H) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) esc += __shfl_xor(esc, o, kWave);
+  if (lane == 0) {
+    base[c] = bs;
+    esc_count[c] = esc;
+    if (esc > 0) atomicAdd(stats, static_cast<unsigned long long>(esc));
+    if (esc > 12) atomicAdd(stats + 1, 1ull);
+    if (esc > 28) atomicAdd(stats + 2, 1ull);
+    if (esc > 60) atomicAdd(stats + 3, 1ull);
+  }
+}
+
+// the median of one chunk (one wavefront) and its base and escape count for both widths
+__device__ __forceinline__ void chunk_stats(const int *__restrict__ ci, int nnz, int chunk0, int nchunks, int c, int *__restrict__ base,
+                                            int *__restrict__ esc_count, unsigned long long *stats) {
   const int lane = threadIdx.x & (kWave - 1);
-  const long long c_ll = static_cast<long long>(blockIdx.x) * (kThreads / kWave) + threadIdx.x / kWave;
-  if (c_ll >= nchunks) return; // wave-uniform
-  const int c = static_cast<int>(c_ll);
   const long long j0 = (static_cast<long long>(chunk0) + c) * kChunk + 4 * lane;
   int col[4];
 #pragma unroll
@@ -63,27 +104,24 @@ __global__ __launch_bounds__(kThreads) void col16_base_kernel(const int *__restr
   const unsigned long long holder = __ballot(rank == want);
   const int src = holder ? __ffsll(static_cast<long long>(holder)) - 1 : 0;
   const int median = __shfl(mine, src, kWave);
-  long long b = static_cast<long long>(median) - 32767;
-  if (valid == 0 || b < 0) b = 0;
-  const int bs = static_cast<int>(b);
-  int esc = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (col[e] != INT_MAX) {
-      const long long d = static_cast<long long>(col[e]) - bs;
-      esc += (d < 0 || d > 65534) ? 1 : 0;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) esc += __shfl_xor(esc, o, kWave);
-  if (lane == 0) {
-    base[c] = bs;
-    esc_count[c] = esc;
-    if (esc > 0) atomicAdd(stats, static_cast<unsigned long long>(esc));
-    if (esc > 12) atomicAdd(stats + 1, 1ull);
-    if (esc > 28) atomicAdd(stats + 2, 1ull);
-    if (esc > 60) atomicAdd(stats + 3, 1ull);
-  }
+  chunk_base<16>(col, median, valid == 0, lane, c, base, esc_count, stats);
+  chunk_base<8>(col, median, valid == 0, lane, c, base + nchunks + 1, esc_count + nchunks + 1, stats + 4);
+}
+
+// One wavefront per chunk.  Pass 1: base + escape count of both widths (16-bit: base[c], esc_count[c], stats[0 .. 3]; 8-bit: base[nchunks + 1 + c],
+// esc_count[nchunks + 1 + c], stats[4 .. 7]); stats[0] += escapes, stats[1 .. 3] += chunks with more than 12 / 28 / 60 of them.  The eight
+// counters are tallied per workgroup in LDS and added to memory once per workgroup.  (With one global atomic per chunk and counter this kernel
+// took 4.3 ms on the Hardesty3-sized matrix for one width and 8.6 ms for both -- nearly every chunk there has more than 12 escapes; 0.49 ms now.)
+__global__ __launch_bounds__(kThreads) void col16_base_kernel(const int *__restrict__ ci, int nnz, int chunk0, int nchunks,
+                                                              int *__restrict__ base, int *__restrict__ esc_count,
+                                                              unsigned long long *__restrict__ stats) {
+  __shared__ unsigned long long tally[8];
+  if (threadIdx.x < 8) tally[threadIdx.x] = 0;
+  __syncthreads();
+  const long long c_ll = static_cast<long long>(blockIdx.x) * (kThreads / kWave) + threadIdx.x / kWave;
+  if (c_ll < nchunks) chunk_stats(ci, nnz, chunk0, nchunks, static_cast<int>(c_ll), base, esc_count, tally); // (wave-uniform)
+  __syncthreads();
+  if (threadIdx.x < 8 && tally[threadIdx.x] != 0) atomicAdd(stats + threadIdx.x, tally[threadIdx.x]);
 }
 
 // esc_count[c] -> max(0, esc_count[c] - E), in place (the input of the exclusive scan that places the overflow escapes)
@@ -96,10 +134,13 @@ __global__ __launch_bounds__(kThreads) void col16_overflow_kernel(int *__restric
 }
 
 // Pass 2 (after the exclusive scan of the overflow counts): offsets, records, overflow list.  rec is pre-zeroed.
+template <int BITS>
 __global__ __launch_bounds__(kThreads) void col16_encode_kernel(const int *__restrict__ ci, int nnz, int chunk0, int nchunks,
                                                                 const int *__restrict__ base, const int *__restrict__ ovf_start,
-                                                                int R, unsigned short *__restrict__ d16, int *__restrict__ rec,
-                                                                int *__restrict__ ovf) {
+                                                                int R, typename CodeWidth<BITS>::T *__restrict__ codes,
+                                                                int *__restrict__ rec, int *__restrict__ ovf) {
+  typedef typename CodeWidth<BITS>::T Code;
+  constexpr int ESC = 2 * CodeWidth<BITS>::half + 1;
   const int lane = threadIdx.x & (kWave - 1);
   const long long c_ll = static_cast<long long>(blockIdx.x) * (kThreads / kWave) + threadIdx.x / kWave;
   if (c_ll >= nchunks) return;
@@ -114,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void col16_encode_kernel(const int *__res
   for (int e = 0; e < 4; ++e) {
     col[e] = (j0 + e < nnz) ? ci[j0 + e] : bs; // padding decodes to the base column (never read as a product)
     const long long d = static_cast<long long>(col[e]) - bs;
-    is_esc[e] = d < 0 || d > 65534;
+    is_esc[e] = d < 0 || d >= ESC;
     mine += is_esc[e] ? 1 : 0;
   }
   // exclusive prefix of the lanes' escape counts
@@ -128,19 +169,19 @@ __global__ __launch_bounds__(kThreads) void col16_encode_kernel(const int *__res
   int pos = incl - mine;
   int *r = rec + static_cast<size_t>(c) * R;
   const int o0 = ovf_start[c];
-  unsigned short out[4];
+  Code out[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    out[e] = 0xFFFF;
+    out[e] = static_cast<Code>(ESC);
     if (is_esc[e]) {
       if (pos < E) r[4 + pos] = col[e];
       else ovf[o0 + pos - E] = col[e];
       ++pos;
     } else {
-      out[e] = static_cast<unsigned short>(col[e] - bs);
+      out[e] = static_cast<Code>(col[e] - bs);
     }
   }
-  unsigned short *dst = d16 + static_cast<size_t>(c) * kChunk + 4 * lane; // (d16 holds whole chunks: the padding is written too)
+  Code *dst = codes + static_cast<size_t>(c) * kChunk + 4 * lane; // (the codes are whole chunks: the padding is written too)
 #pragma unroll
   for (int e = 0; e < 4; ++e) dst[e] = out[e];
   if (lane == 0) {
@@ -184,11 +225,16 @@ bool launch_col16_scan(hipStream_t stream, int nchunks, const int *esc_count, in
 }
 
 void launch_col16_encode(hipStream_t stream, const int *ci, int nnz, int chunk0, int nchunks, const int *base, const int *ovf_start,
-                         int R, unsigned short *d16, int *rec, int *ovf) {
+                         int R, int bits, void *codes, int *rec, int *ovf) {
   if (nchunks <= 0) return;
   const int waves_per_block = kThreads / kWave;
-  SPMV_ACC_LAUNCH(col16_encode_kernel, dim3((nchunks + waves_per_block - 1) / waves_per_block), dim3(kThreads), 0, stream, ci, nnz,
-                     chunk0, nchunks, base, ovf_start, R, d16, rec, ovf);
+  const dim3 grid((nchunks + waves_per_block - 1) / waves_per_block);
+  if (bits == 8)
+    SPMV_ACC_LAUNCH(col16_encode_kernel<8>, grid, dim3(kThreads), 0, stream, ci, nnz, chunk0, nchunks, base, ovf_start, R,
+                       static_cast<unsigned char *>(codes), rec, ovf);
+  else
+    SPMV_ACC_LAUNCH(col16_encode_kernel<16>, grid, dim3(kThreads), 0, stream, ci, nnz, chunk0, nchunks, base, ovf_start, R,
+                       static_cast<unsigned short *>(codes), rec, ovf);
 }
 
 void launch_col16_guard(hipStream_t stream, const int *ci, int lo, int span, int *out) {

@@ -45,8 +45,10 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 }
 
 // HINT: gather hints (k_hint.hip): the block's gathers take their cache policy from the plan's cold bits.
-// C16: the non-zeros' columns come from the plan's 16-bit encoding (k_col16.hip) instead of colindex: 2.25 B instead of 4 B of stream per
-// non-zero.  The tile origin is then aligned down to a 256-non-zero chunk (a wavefront's step = one chunk record) instead of to 4.
+// C16: the non-zeros' columns come from the plan's column encoding (k_col16.hip) instead of colindex: 2.25 B (16-bit codes) or 1.25 B (8-bit
+// codes; both with 16-int records) instead of 4 B of stream per non-zero.  The tile origin is then aligned down to a 256-non-zero chunk (a
+// wavefront's step = one chunk record) instead of to 4.  The code width is a grid-uniform branch inside the staging (tile_stage.hpp
+// stage_products_c16), not a template parameter: one instance reads both widths, within the same 64 VGPRs.
 template <int VEC, bool NTC, bool NTV, bool LENS, bool HINT = false, bool C16 = false>
 __global__ __launch_bounds__(kThreads) void rowblock_stream_kernel(int m, int nnz, int nblocks, int rpb, int flags,
                                                                    double alpha, double beta,

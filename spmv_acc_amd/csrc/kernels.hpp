@@ -155,14 +155,16 @@ constexpr int kRowblockMaxRounds = 8;
 // (hip-flat/flat_imp.inl:108-131) computed by one binary search per entry; no memset needed.
 void launch_break_points(hipStream_t stream, const int *rp, int m, int nnz, int stride, int *bp, int bp_len);
 
-// ---- 16-bit column encoding (k_col16.hip builds it, tile_stage.hpp stage_products_c16 reads it) -----------------------------------
+// ---- 16-/8-bit column encoding (k_col16.hip builds it, tile_stage.hpp stage_products_c16 reads it) --------------------------------
 constexpr int kCol16Chunk = 256; // non-zeros per base column: one wavefront's step of the tile kernels (64 lanes x 4), aligned in the absolute non-zero index
 struct Col16 {
   int state = -1;                // -1 not looked at, 0 not worth it on this matrix (too many escapes, x of 4 GB or more), 1 built
   int chunk0 = 0;                // the view's first chunk: A.nnz0 rounded down to a flat tile (2048), in chunks (0 unless the matrix is an un-rebased row sub-range); tables are indexed by chunk - chunk0
   int nchunks = 0;
   int rec_ints = 0;              // R: ints per chunk record (16, 32 or 64): {base, escapes, overflow start, 0, first R - 4 escaped columns}
+  int bits = 0;                  // code width: 16 (d16 holds the codes) or 8 (d8 does; the other array is null)
   unsigned short *d16 = nullptr; // nchunks * 256 offsets from the chunk's base; 0xFFFF = escape
+  unsigned char *d8 = nullptr;   // nchunks * 256 offsets from the chunk's base; 0xFF = escape
   int *rec = nullptr;            // nchunks * R
   int *ovf = nullptr;            // escapes beyond R - 4 per chunk, chunk by chunk (+ 64 entries of padding)
   int *ci_guard = nullptr;       // 64 samples of colindex taken at build time (stale-plan guard of the kernels that no longer read colindex)
@@ -172,7 +174,8 @@ struct Col16 {
 };
 // what a kernel gets (by value): the tables pre-offset so that the kernel indexes them by ABSOLUTE chunk / non-zero index
 struct Col16Dev {
-  const unsigned short *d16;
+  const unsigned short *d16; // (null with 8-bit codes)
+  const unsigned char *d8;   // (null with 16-bit codes)
   const int *rec;
   const int *ovf;
   const int *ci_guard;
@@ -181,7 +184,8 @@ struct Col16Dev {
 };
 inline Col16Dev col16_dev(const Col16 &C, const CsrDev &A) {
   Col16Dev d;
-  d.d16 = C.d16 - static_cast<long long>(C.chunk0) * kCol16Chunk;
+  d.d16 = C.d16 ? C.d16 - static_cast<long long>(C.chunk0) * kCol16Chunk : nullptr;
+  d.d8 = C.d8 ? C.d8 - static_cast<long long>(C.chunk0) * kCol16Chunk : nullptr;
   d.rec = C.rec - static_cast<long long>(C.chunk0) * C.rec_ints;
   d.ovf = C.ovf;
   d.ci_guard = C.ci_guard;
@@ -199,11 +203,13 @@ void launch_hint_hist(hipStream_t stream, const unsigned *counts, int nlines, un
 void launch_hint_bits(hipStream_t stream, const int *ci, int nnz, int ncols, const unsigned *counts, unsigned threshold, unsigned char *bits);
 
 size_t col16_scan_bytes(int nchunks);
+// base / esc_count: [0 .. nchunks) for 16-bit codes, [nchunks + 1 .. 2 nchunks + 1) for 8-bit codes; stats[0 .. 3] 16-bit, stats[4 .. 7] 8-bit
 void launch_col16_base(hipStream_t stream, const int *ci, int nnz, int chunk0, int nchunks, int *base, int *esc_count, unsigned long long *stats);
 void launch_col16_overflow(hipStream_t stream, int *cnt, int nchunks, int E);
 bool launch_col16_scan(hipStream_t stream, int nchunks, const int *esc_count, int *esc_start, void *tmp, size_t tmp_bytes);
+// bits 16: codes = unsigned short[nchunks * 256]; bits 8: unsigned char[nchunks * 256]
 void launch_col16_encode(hipStream_t stream, const int *ci, int nnz, int chunk0, int nchunks, const int *base, const int *ovf_start, int R,
-                         unsigned short *d16, int *rec, int *ovf);
+                         int bits, void *codes, int *rec, int *ovf);
 void launch_col16_guard(hipStream_t stream, const int *ci, int lo, int span, int *out);
 
 // flat family: one workgroup per `stride` non-zeros (stride = kThreads * {4, 8, 16}); complete rows are

@@ -560,6 +560,7 @@ bool query_plan(const int *d_rowptr, int m, PlanInfo *out) {
       out->settled = p.calls > 0 && !p.tuning_open ? 1 : 0;
       out->last_kernel = p.last_kernel;
       out->col16 = p.last_c16;
+      out->col_bits = p.last_col_bits;
       out->slab_passes = p.seg_state == 1 && (tun(kT_slab_segments) >= 1 || (tun(kT_slab_segments) < 0 && p.seg_choice == 1)) ? p.seg_slabs - (p.seg_rest_below > 0 ? 1 : 0) : 0; // (column slabs: the whole-row pass of the two-class form is not counted)
       return true;
     }

@@ -228,20 +228,21 @@ __device__ __forceinline__ void stage_finish(double *__restrict__ lds, const Str
   }
 }
 
-// ---- staging from the 16-bit column encoding (k_col16.hip, kernels.hpp Col16) --------------------------------------------------------
+// ---- staging from the 16-/8-bit column encoding (k_col16.hip, kernels.hpp Col16) --------------------------------------------------------
 // The branch-free step of stage_products with the colindex stream (4 B per non-zero) replaced by the plan's encoding: per lane and step one
-// 8-B load of four 16-bit offsets, per wavefront and step ONE load of the chunk's record (R ints: base, escape count, overflow start, the
-// chunk's first R - 4 escaped columns).  The tile origin a0 is a multiple of 256, so a wavefront's step is exactly one chunk and the
-// record's address depends on nothing but the step: records, offsets and values are all requested before anything is waited for (records
-// first: they come back first and the gathers need only them and the offsets).  Decoding: base from lane 0 of the record (a scalar), column
-// = base + offset; in a chunk WITH escapes (wave-uniform test on the record's count) an escaped entry takes its column out of the record by
-// rank -- ballots + popcounts for the rank, one ds_bpermute per element slot that holds an escape anywhere in the wavefront; only a chunk
-// with more than R - 4 escapes reads the overflow list (a dependent load, <= 1 % of the chunks by the choice of R).
+// 8-B load of four 16-bit offsets (or one 4-B load of four 8-bit ones), per wavefront and step ONE load of the chunk's record (R ints: base,
+// escape count, overflow start, the chunk's first R - 4 escaped columns).  The tile origin a0 is a multiple of 256, so a wavefront's step is
+// exactly one chunk and the record's address depends on nothing but the step: records, offsets and values are all requested before anything is
+// waited for (records first: they come back first and the gathers need only them and the offsets).  Decoding: base from lane 0 of the record (a
+// scalar), column = base + offset; in a chunk WITH escapes (wave-uniform test on the record's count) an escaped entry takes its column out of the
+// record by rank -- ballots + popcounts for the rank, one ds_bpermute per element slot that holds an escape anywhere in the wavefront; only a
+// chunk with more than R - 4 escapes reads the overflow list (a dependent load, <= 1 % of the chunks by the choice of R).
 // (A form whose codes NAME the escape -- 0xFF00 + index, no ranks: 16 instead of ~40 vector instructions per four non-zeros, 4 more registers --
 // measured the same within 0.5 % on eight stand-ins under pinned plans and 2-4 % slower on the long-row one: profiles/r06_col16_counters.md
-// section 5.  The instruction count was not what held this path back; the wait in front of the first decode was: see stage_products_c16_body.)
+// section 5.  The instruction count was not what held this path back; the wait in front of the first decode was: see stage_products_c16_all.)
 // (Round 2's form -- base[] and esc_start[] arrays, one escape list -- needed two scalars back before it could ask for the escapes, and those
 // before the first gather: profiles/r06_col16_counters.md.)
+// The code width is the plan's (C.d8 set: 8 bits), a grid-uniform branch in front of the bodies: the kernels keep one instance per staging form.
 //   a0  : tile origin, multiple of 256;   lo4 : first group the workgroup needs (multiple of 4, a0 <= lo4);   hi : exclusive bound
 // Lanes whose group lies outside [lo4, hi) still load their own offsets (the ranks count every escape of the chunk) but re-read the values of
 // group lo4 and gather the chunk's base column (L1 hits, no extra lines); their products land in slots no reader touches.
@@ -249,17 +250,49 @@ __device__ __forceinline__ void stage_finish(double *__restrict__ lds, const Str
 typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
 typedef uint2v uint2v_a2 __attribute__((aligned(2)));
 
-// One step's decode: the four columns of this lane's group out of the record (held one entry per lane in rv) and the four codes dq.
-__device__ __forceinline__ void c16_decode(int (&c)[4], const uint2v d, int rv, int R, int lane, const int *__restrict__ ovf) {
+// the four codes of one lane and step
+template <int BITS> struct Codes4;
+template <> struct Codes4<16> {
+  static constexpr int escape = 0xFFFF;
+  uint2v d;
+  template <bool NT> __device__ __forceinline__ void load(const Col16Dev &C, int j) {
+    const uint2v_a2 *p = reinterpret_cast<const uint2v_a2 *>(C.d16 + j); // (the offsets are padded to whole chunks)
+    d = NT ? __builtin_nontemporal_load(p) : *p;
+  }
+  __device__ __forceinline__ void split(int (&dq)[4]) const {
+    dq[0] = static_cast<int>(d.x & 0xFFFFu);
+    dq[1] = static_cast<int>(d.x >> 16);
+    dq[2] = static_cast<int>(d.y & 0xFFFFu);
+    dq[3] = static_cast<int>(d.y >> 16);
+  }
+};
+template <> struct Codes4<8> {
+  static constexpr int escape = 0xFF;
+  unsigned d;
+  template <bool NT> __device__ __forceinline__ void load(const Col16Dev &C, int j) {
+    const unsigned *p = reinterpret_cast<const unsigned *>(C.d8 + j); // (j is a multiple of 4: an aligned 4-B load)
+    d = NT ? __builtin_nontemporal_load(p) : *p;
+  }
+  __device__ __forceinline__ void split(int (&dq)[4]) const {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dq[q] = static_cast<int>((d >> (8 * q)) & 0xFFu);
+  }
+};
+
+// One step's decode: the four columns of this lane's group out of the record (held one entry per lane in rv) and the four codes.
+template <int BITS>
+__device__ __forceinline__ void c16_decode(int (&c)[4], const Codes4<BITS> &d, int rv, int R, int lane, const int *__restrict__ ovf) {
+  constexpr int ESC = Codes4<BITS>::escape;
   const int bs = __builtin_amdgcn_readlane(rv, 0);
   const int nesc = __builtin_amdgcn_readlane(rv, 1);
-  const int dq[4] = {static_cast<int>(d.x & 0xFFFFu), static_cast<int>(d.x >> 16), static_cast<int>(d.y & 0xFFFFu), static_cast<int>(d.y >> 16)};
+  int dq[4];
+  d.split(dq);
 #pragma unroll
   for (int q = 0; q < 4; ++q) c[q] = bs + dq[q];
   if (nesc > 0) { // wave-uniform
     const int E = R - 4;
     const unsigned long long lt = (1ull << lane) - 1ull;
-    const bool e[4] = {dq[0] == 0xFFFF, dq[1] == 0xFFFF, dq[2] == 0xFFFF, dq[3] == 0xFFFF};
+    const bool e[4] = {dq[0] == ESC, dq[1] == ESC, dq[2] == ESC, dq[3] == ESC};
     const unsigned long long slot[4] = {__ballot(e[0]), __ballot(e[1]), __ballot(e[2]), __ballot(e[3])};
     // rank of this lane's first escape in the chunk: the escapes held by lower lanes (records list them in non-zero order)
     int r = __popcll(slot[0] & lt) + __popcll(slot[1] & lt) + __popcll(slot[2] & lt) + __popcll(slot[3] & lt);
@@ -278,11 +311,11 @@ __device__ __forceinline__ void c16_decode(int (&c)[4], const uint2v d, int rv, 
 // waitcnt pass cannot count across them: it placed s_waitcnt vmcnt(0) in front of the first decode (ALL the value loads back before the first
 // gather leaves) where vmcnt(5) is what the decode needs (record + offsets) -- 2-5 % of these kernels' time on the FEM-class stand-ins
 // (profiles/r06_col16_counters.md section 5).  Seven of eight wavefronts of a row-block grid take this body (tiles are filled to 1800 of 2048).
-template <int THREADS, int NPT, bool NTC, bool NTV>
+template <int THREADS, int NPT, bool NTC, bool NTV, int BITS>
 __device__ __forceinline__ void stage_products_c16_all(double *__restrict__ lds, int a0, int lo4, int hi, const Col16Dev &C,
                                                        const double *__restrict__ v, const double *__restrict__ x) {
   constexpr int K = NPT / 4;
-  uint2v d[K];
+  Codes4<BITS> d[K];
   double2v va[K], vb[K];
   int rv[K];
   const int lane = threadIdx.x & (kWave - 1);
@@ -294,11 +327,7 @@ __device__ __forceinline__ void stage_products_c16_all(double *__restrict__ lds,
     rv[k] = C.rec[static_cast<long long>(wave_j >> 8) * R + rl];
   }
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int j = a0 + 4 * (threadIdx.x + k * THREADS);
-    const uint2v_a2 *p = reinterpret_cast<const uint2v_a2 *>(C.d16 + j); // (the offsets are padded to whole chunks)
-    d[k] = NTC ? __builtin_nontemporal_load(p) : *p;
-  }
+  for (int k = 0; k < K; ++k) d[k].template load<NTC>(C, a0 + 4 * (threadIdx.x + k * THREADS));
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int j = a0 + 4 * (threadIdx.x + k * THREADS);
@@ -332,7 +361,7 @@ __device__ __forceinline__ void stage_products_c16_all(double *__restrict__ lds,
 }
 
 // The wavefronts at a tile's end: one step at a time, not unrolled (see stage_products_tail).
-template <int THREADS, int NPT, bool NTC, bool NTV>
+template <int THREADS, int NPT, bool NTC, bool NTV, int BITS>
 __device__ __forceinline__ void stage_products_c16_tail(double *__restrict__ lds, int a0, int lo4, int hi, const Col16Dev &C,
                                                         const double *__restrict__ v, const double *__restrict__ x) {
   const int lane = threadIdx.x & (kWave - 1);
@@ -345,8 +374,8 @@ __device__ __forceinline__ void stage_products_c16_tail(double *__restrict__ lds
     const int g = threadIdx.x + k * THREADS;
     const int j = a0 + 4 * g;
     const int rv = C.rec[static_cast<long long>(wave_j >> 8) * R + rl];
-    const uint2v_a2 *p = reinterpret_cast<const uint2v_a2 *>(C.d16 + j);
-    const uint2v d = NTC ? __builtin_nontemporal_load(p) : *p;
+    Codes4<BITS> d;
+    d.template load<NTC>(C, j);
     const int jv = (j >= lo4 && j < hi) ? j : lo4;
     const double2v va = load_stream_d2<NTV>(v + jv), vb = load_stream_d2<NTV>(v + jv + 2);
     int c[4];
@@ -372,8 +401,13 @@ __device__ __forceinline__ void stage_products_c16(double *__restrict__ lds, int
                                                    const double *__restrict__ v, const double *__restrict__ x) {
   // the wavefront's LAST step starts below hi: so do all its steps (wave-uniform)
   const int last_j = __builtin_amdgcn_readfirstlane(a0 + 4 * ((threadIdx.x & ~(kWave - 1)) + (NPT / 4 - 1) * THREADS));
-  if (last_j < hi) stage_products_c16_all<THREADS, NPT, NTC, NTV>(lds, a0, lo4, hi, C, v, x);
-  else stage_products_c16_tail<THREADS, NPT, NTC, NTV>(lds, a0, lo4, hi, C, v, x);
+  if (C.d8 != nullptr) { // the plan's code width (grid-uniform)
+    if (last_j < hi) stage_products_c16_all<THREADS, NPT, NTC, NTV, 8>(lds, a0, lo4, hi, C, v, x);
+    else stage_products_c16_tail<THREADS, NPT, NTC, NTV, 8>(lds, a0, lo4, hi, C, v, x);
+  } else {
+    if (last_j < hi) stage_products_c16_all<THREADS, NPT, NTC, NTV, 16>(lds, a0, lo4, hi, C, v, x);
+    else stage_products_c16_tail<THREADS, NPT, NTC, NTV, 16>(lds, a0, lo4, hi, C, v, x);
+  }
 }
 
 // Stale-plan guard of the kernels that read the encoding: they no longer read colindex, so an in-place edit of the column indices (same rowptr)

@@ -320,15 +320,17 @@ bool ensure_col16(Plan &p, hipStream_t st) {
   void *tmp = nullptr;
   const size_t tmp_bytes = col16_scan_bytes(nchunks);
   const size_t n1 = static_cast<size_t>(nchunks) + 1;
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void **>(&base), sizeof(int) * n1), "hipMalloc col16 bases") &&
-            hip_ok(hipMalloc(reinterpret_cast<void **>(&cnt), sizeof(int) * n1), "hipMalloc col16 escape counts") &&
+  // bases and escape counts of both code widths: [0, n1) 16-bit, [n1, 2 n1) 8-bit (k_col16.hip col16_base_kernel)
+  bool ok = hip_ok(hipMalloc(reinterpret_cast<void **>(&base), sizeof(int) * 2 * n1), "hipMalloc col16 bases") &&
+            hip_ok(hipMalloc(reinterpret_cast<void **>(&cnt), sizeof(int) * 2 * n1), "hipMalloc col16 escape counts") &&
             hip_ok(hipMalloc(reinterpret_cast<void **>(&ovf_start), sizeof(int) * n1), "hipMalloc col16 overflow offsets") &&
-            hip_ok(hipMalloc(reinterpret_cast<void **>(&stats), sizeof(unsigned long long) * 4), "hipMalloc col16 statistics") &&
+            hip_ok(hipMalloc(reinterpret_cast<void **>(&stats), sizeof(unsigned long long) * 8), "hipMalloc col16 statistics") &&
             hip_ok(hipMalloc(&tmp, tmp_bytes > 0 ? tmp_bytes : 16), "hipMalloc col16 scan workspace") &&
             hip_ok(hipMemsetAsync(cnt + nchunks, 0, sizeof(int), st), "memset col16") &&
-            hip_ok(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 4, st), "memset col16 statistics");
-  unsigned long long h_stats[4] = {0, 0, 0, 0};
-  int R = 0, total = 0;
+            hip_ok(hipMemsetAsync(cnt + n1 + nchunks, 0, sizeof(int), st), "memset col16") &&
+            hip_ok(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 8, st), "memset col16 statistics");
+  unsigned long long h_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int R = 0, total = 0, bits = 16;
   if (ok) {
     launch_col16_base(st, A.ci, A.nnz, chunk0, nchunks, base, cnt, stats);
     ok = hip_ok(hipMemcpyAsync(h_stats, stats, sizeof(h_stats), hipMemcpyDeviceToHost, st), "read col16 statistics") &&
@@ -337,30 +339,43 @@ bool ensure_col16(Plan &p, hipStream_t st) {
   if (ok) {
     const unsigned long long limit = static_cast<unsigned long long>(nchunks) / 100; // chunks allowed to overflow their record
     R = h_stats[1] <= limit ? 16 : (h_stats[2] <= limit ? 32 : (h_stats[3] <= limit ? 64 : 0));
+    // 8-bit codes by rule (no timing: the kernel is the same, one load narrower): where their record size is the same (the 8-bit escapes of a chunk
+    // include its 16-bit ones, so it is never smaller) and they add at most 0.5 % of the non-zeros in escapes
+    const int R8 = h_stats[5] <= limit ? 16 : (h_stats[6] <= limit ? 32 : (h_stats[7] <= limit ? 64 : 0));
+    const long long extra8 = static_cast<long long>(h_stats[4]) - static_cast<long long>(h_stats[0]);
+    const int mode = tun(kT_col16);
+    bits = mode == 8 || (mode != 2 && R > 0 && R8 > 0 && R8 <= R && 200 * extra8 <= static_cast<long long>(A.count())) ? 8 : 16; // (col16 = 8 / 2 pin the width)
+    if (bits == 8) R = R8;
     const int forced = tun(kT_col16) > 1 ? tun(kT_col16) : 0; // (tests: col16 = 16 / 32 / 64 pins the record size, overflow or not)
     if (forced == 16 || forced == 32 || forced == 64) R = forced;
     tune_log("m %d nnz %d 16-bit columns: %llu escapes in %d chunks, %llu / %llu / %llu chunks above 12 / 28 / 60 -> %s", A.m, A.nnz, h_stats[0], nchunks,
              h_stats[1], h_stats[2], h_stats[3], R ? (R == 16 ? "16-int records" : (R == 32 ? "32-int records" : "64-int records")) : "not encoded");
+    tune_log("m %d nnz %d 8-bit columns: %llu escapes (%+lld), %llu / %llu / %llu chunks above 12 / 28 / 60 -> %d-bit codes", A.m, A.nnz, h_stats[4], extra8,
+             h_stats[5], h_stats[6], h_stats[7], bits);
   }
   if (ok && R > 0) {
-    launch_col16_overflow(st, cnt, nchunks, R - 4);
-    ok = launch_col16_scan(st, nchunks, cnt, ovf_start, tmp, tmp_bytes) &&
+    const size_t cofs = bits == 8 ? n1 : 0; // the chosen width's bases and escape counts
+    launch_col16_overflow(st, cnt + cofs, nchunks, R - 4);
+    ok = launch_col16_scan(st, nchunks, cnt + cofs, ovf_start, tmp, tmp_bytes) &&
          hip_ok(hipMemcpyAsync(&total, ovf_start + nchunks, sizeof(int), hipMemcpyDeviceToHost, st), "read col16 overflow total") &&
          hip_ok(hipStreamSynchronize(st), "sync col16");
-    const size_t d16_bytes = sizeof(unsigned short) * static_cast<size_t>(nchunks) * kCol16Chunk;
+    const size_t code_bytes = static_cast<size_t>(bits / 8) * static_cast<size_t>(nchunks) * kCol16Chunk;
     const size_t rec_bytes = sizeof(int) * static_cast<size_t>(nchunks) * R;
     const size_t ovf_bytes = sizeof(int) * (static_cast<size_t>(total) + 64);
-    ok = ok && hip_ok(hipMalloc(reinterpret_cast<void **>(&C.d16), d16_bytes), "hipMalloc col16 offsets") &&
+    void *codes = nullptr;
+    ok = ok && hip_ok(hipMalloc(&codes, code_bytes), "hipMalloc col16 offsets") &&
          hip_ok(hipMalloc(reinterpret_cast<void **>(&C.rec), rec_bytes), "hipMalloc col16 records") &&
          hip_ok(hipMalloc(reinterpret_cast<void **>(&C.ovf), ovf_bytes), "hipMalloc col16 overflow list") &&
          hip_ok(hipMalloc(reinterpret_cast<void **>(&C.ci_guard), sizeof(int) * kGuardSamples), "hipMalloc col16 guard") &&
          hip_ok(hipMemsetAsync(C.rec, 0, rec_bytes, st), "memset col16 records") && hip_ok(hipMemsetAsync(C.ovf, 0, ovf_bytes, st), "memset col16 overflow");
+    if (bits == 8) C.d8 = static_cast<unsigned char *>(codes);
+    else C.d16 = static_cast<unsigned short *>(codes);
     if (ok) {
-      launch_col16_encode(st, A.ci, A.nnz, chunk0, nchunks, base, ovf_start, R, C.d16, C.rec, C.ovf);
+      launch_col16_encode(st, A.ci, A.nnz, chunk0, nchunks, base + cofs, ovf_start, R, bits, codes, C.rec, C.ovf);
       launch_col16_guard(st, A.ci, A.nnz0, A.count() > 0 ? A.count() - 1 : 0, C.ci_guard);
       ok = hip_ok(hipStreamSynchronize(st), "sync col16 encode");
     }
-    C.bytes = d16_bytes + rec_bytes + ovf_bytes;
+    C.bytes = code_bytes + rec_bytes + ovf_bytes;
   }
   for (void *q : {static_cast<void *>(base), static_cast<void *>(cnt), static_cast<void *>(ovf_start), static_cast<void *>(stats), tmp})
     if (q) (void)hipFree(q);
@@ -377,7 +392,8 @@ bool ensure_col16(Plan &p, hipStream_t st) {
   C.chunk0 = chunk0;
   C.nchunks = nchunks;
   C.rec_ints = R;
-  C.escapes = static_cast<long long>(h_stats[0]);
+  C.bits = bits;
+  C.escapes = static_cast<long long>(h_stats[bits == 8 ? 4 : 0]);
   C.overflow = total;
   return true;
 }
