@@ -111,6 +111,62 @@ int spmv_acc_csr_spmm(int layout, int k, double alpha, double beta, int m, int n
                       const int *d_rowptr, const int *d_colindex, const double *d_value,
                       const double *dX, long long ldx, double *dY, long long ldy);
 
+/* ---- the transposed product, 1: a stable device transpose into caller-owned arrays (new) -------------------------------------------
+ * replaces: nothing in the reference; it never reads `trans`, api/spmv.h:13.  (The `trans` argument of every other entry keeps its
+ * behaviour: a non-zero value is reported as SPMV_ACC_ERR_UNSUPPORTED_TRANS and the non-transposed product is computed.)
+ * Writes the CSR of A^T (the CSC of A) for the m x n matrix A: d_t_rowptr (n + 1 ints), d_t_colindex (nnz ints: the source ROW of each
+ * entry), d_t_value (nnz doubles) and, where d_perm is not NULL, d_perm (nnz ints: the source position q of output entry p).  d_value and
+ * d_t_value may both be NULL: structure only.  The caller owns the outputs and runs ANY entry of this library on them as an n x m matrix
+ * -- every strategy, spmv_acc_prepare, the SpMM entry, the shards -- so the whole tuned engine serves y = alpha * A^T * x + beta * y.
+ * STABLE and deterministic: inside output row c the entries appear in ascending source position, so the outputs are a pure function of
+ * the inputs, bit for bit a host stable argsort of colindex (one radix sort of the (column, position) pairs; no float is added).
+ * nnz < 0: rowptr[m] is read from the device.  The matrix must be rebased (rowptr[0] == 0; else SPMV_ACC_ERR_BAD_ARGUMENT), and a given
+ * nnz must be rowptr[m].  m == 0, n == 0 or nnz == 0: d_t_rowptr is set to zeros, nothing else is written.  A column outside [0, n) is
+ * never turned into an address: the columns are counted first, and if one is out of range nothing is written and
+ * SPMV_ACC_ERR_BAD_ARGUMENT is returned.  Null pointers where data is needed, negative m or n: SPMV_ACC_ERR_BAD_ARGUMENT, nothing is
+ * launched; m, n or nnz beyond int32 block arithmetic: SPMV_ACC_ERR_TOO_LARGE.
+ * Runs on the calling thread's library stream and has finished when it returns (it allocates about 8 B per non-zero of workspace -- 12 B
+ * without d_perm -- plus the sort's scratch, synchronises, and frees all of it, on the error paths too).  Inside a stream capture it
+ * enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan.  After an in-place edit of `value` the next entry
+ * refreshes d_t_value; after a change of structure transpose again (and release the plans of the old transposed arrays).
+ * Cost and when to use it: see the third entry below.  Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error). */
+int spmv_acc_csr_transpose(int m, int n, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
+                           int *d_t_rowptr, int *d_t_colindex, double *d_t_value, int *d_perm);
+
+/* ---- the transposed product, 2: values changed in place (new) ------------------------------------------------------------------------
+ * replaces: nothing in the reference.  d_t_value[p] = d_value[d_perm[p]] for p < nnz, with the d_perm an earlier transpose of the same
+ * structure returned: the structure is transposed once, the values follow at the cost of one gather pass.  One kernel on the calling
+ * thread's library stream: asynchronous, no allocation, may be captured.  The explicit, caller-driven counterpart of
+ * spmv_acc_refresh_values (no plan holds a copy of the caller's values on this route).  An entry of d_perm outside [0, nnz) is skipped.
+ * Returns 0 or an spmv_acc_error code. */
+int spmv_acc_csr_transpose_values(int nnz, const int *d_perm, const double *d_value, double *d_t_value);
+
+/* ---- the transposed product, 3: y = alpha * A^T * x + beta * y straight from the caller's CSR (new) -----------------------------------
+ * replaces: nothing in the reference; it never reads `trans`, api/spmv.h:13.  dx holds m doubles, dy holds n.  For callers who cannot
+ * afford a second copy of the matrix, or who use A^T once.  STATELESS: no plan, no cache entry, no timing; nothing derived from the
+ * caller's arrays survives the call.  So it is launches only from its FIRST call on a matrix and may always be captured into a hipGraph
+ * (nnz < 0 reads rowptr[m] from the device and is refused inside a capture).  Two launches on the calling thread's library stream:
+ * y = beta * y (beta == 0: y is written and never read, NaNs in it do not propagate; beta == 1: skipped), then one pass over the
+ * non-zeros in storage order that adds alpha * a * x[row] to y[col] with fp64 hardware atomic adds.  alpha == 0 or nnz == 0: the first
+ * launch only.  The non-zero stream is cut into fixed tiles, so the time does not depend on how the rows are distributed.
+ * THE ONE ENTRY WHOSE SUMS DEPEND ON ARRIVAL ORDER: two calls on the same data may differ in the last bits of y (the error stays within
+ * the usual bound relative to |alpha| * sum |a| |x| + |beta y|).  With tunable "deterministic" = 1 it enqueues nothing and returns
+ * SPMV_ACC_ERR_BAD_ARGUMENT: use spmv_acc_csr_transpose and the ordinary product on its result, which is bitwise reproducible.
+ * d_rowptr may be an un-rebased row sub-range (rowptr + r0 with the whole colindex / value arrays and nnz = the END offset
+ * rowptr[r0 + m], the convention of the shards): a rank then gets its partial A_local^T * x_local.  Every column is checked in the kernel
+ * and one outside [0, n) is dropped (here it would be a WRITE outside y).  x and y must not overlap (not detected), and y must be
+ * ordinary device memory (hipMalloc): the hardware adds are not defined on fine-grained host-coherent allocations.
+ * Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST, as measured (MI355X, tools/transpose_bench.py, profiles/transpose_bench.md): the pass runs at the rate the chip ADDS, not at the
+ * rate it streams.  Headline stand-in (40.45 M non-zeros, settled SpMV 0.14 ms): 0.92 ms = 0.35 TB/s of added bytes, 6.3 x a settled SpMV on
+ * the transposed copy (8 B per non-zero at the 1.3 TB/s the hardware reaches at its best access shape would be 0.25 ms; this column
+ * pattern reaches a quarter of that).  FEM class (28.2 M): 0.48 ms, 0.47 TB/s, 9.7 x.  Power-law columns (R-MAT 22, 65.2 M): 7.9 ms,
+ * 0.07 TB/s, 16 x -- every lane of an add lands on another line.  The device transpose costs 2.6 / 1.8 / 5.1 ms on the three (18 / 37 / 11
+ * SpMVs), so TRANSPOSE ONCE when A^T is used more than about four times (FEM, headline class) and always on power-law columns; keep this
+ * entry for one or two products and for matrices whose second copy does not fit. */
+int spmv_acc_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *d_rowptr, const int *d_colindex,
+                        const double *d_value, const double *dx, double *dy);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,
@@ -245,7 +301,8 @@ int spmv_acc_prepare_beta(int strategy, double beta, int m, int n, int nnz, cons
  *     matrix, keyed by a digest of (library version, device name, m, n, nnz, 64 rowptr samples); a later process that meets the
  *     same matrix on the same device adopts them and only runs the structural passes (NULL or "" switches it off);
  *   tunable "deterministic" = 1 / environment SPMV_ACC_DETERMINISTIC=1: nothing is timed at all, every choice follows a fixed
- *     rule on the matrix' shape -- y is then bitwise equal across processes and runs (the kernels never use atomics).
+ *     rule on the matrix' shape -- y is then bitwise equal across processes and runs (the kernels never use atomics; the one
+ *     exception, spmv_acc_csr_spmv_t, adds with fp64 atomics and is therefore refused under this switch).
  * Round 6: with the default ("deterministic" = 0) the calls made BEFORE a plan is settled are answered by that same rule (the plan's rule twin)
  * while the timings advance beside them against a scratch y; from the first settled call on the timed choices serve.  y changes its last bits at
  * most once per (matrix, strategy, beta class), at a call spmv_acc_query_plan_settled shows.  "deterministic" = -1: as rounds 2-5 (the timed

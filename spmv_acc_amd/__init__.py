@@ -40,7 +40,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_query_plan_beta0", "spmv_acc_query_plan_slab_passes", "spmv_acc_shard_create", "spmv_acc_shard_step", "spmv_acc_shard_pipeline",
     "spmv_acc_shard_destroy", "spmv_acc_rccl_comm_init_all", "spmv_acc_rccl_comm_destroy", "spmv_acc_set_tune_cache",
     "spmv_acc_prepare_beta", "spmv_acc_time_spmv_events", "spmv_acc_refresh_values", "spmv_acc_time_spmv_region", "spmv_acc_query_plan_last_kernel", "spmv_acc_time_spmv_kernels",
-    "spmv_acc_csr_spmm",
+    "spmv_acc_csr_spmm", "spmv_acc_csr_transpose", "spmv_acc_csr_transpose_values", "spmv_acc_csr_spmv_t",
 )
 
 _lib = None
@@ -137,6 +137,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     ll = ctypes.c_longlong
     lib.spmv_acc_csr_spmm.argtypes = [ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp, vp, ll, vp, ll]
     lib.spmv_acc_csr_spmm.restype = ci
+    lib.spmv_acc_csr_transpose.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.spmv_acc_csr_transpose.restype = ci
+    lib.spmv_acc_csr_transpose_values.argtypes = [ci, vp, vp, vp]
+    lib.spmv_acc_csr_transpose_values.restype = ci
+    lib.spmv_acc_csr_spmv_t.argtypes = [cd, cd, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.spmv_acc_csr_spmv_t.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -290,6 +296,75 @@ def csr_spmm(alpha: float, beta: float, m: int, n: int, nnz: int, rowptr, colind
     lib.spmv_acc_csr_spmm(layout, k, alpha, beta, m, n, nnz, _ptr(h_rowptr), _ptr(rowptr), _ptr(colindex), _ptr(value), _ptr(X), ldx,
                           _ptr(Y), ldy)
     _check(lib)
+
+
+def _require_tensors(**named) -> None:
+    """The transposed entries take torch tensors only (they write through raw pointers and, for csr_transpose, allocate beside them)."""
+    for name, t in named.items():
+        if t is None or not hasattr(t, "is_cuda") or not hasattr(t, "data_ptr"):
+            raise SpmvAccError(f"{name}: a torch tensor on the GPU is required")
+
+
+def csr_spmv_t(alpha: float, beta: float, m: int, n: int, nnz: int, rowptr, colindex, value, x, y) -> None:
+    """y = alpha*A^T*x + beta*y straight from the caller's CSR (spmv_acc_csr_spmv_t, async on torch's current stream): x holds m
+    entries, y holds n.  Stateless (no plan) and capturable from its first call; adds with fp64 atomics, so the last bits of y depend on
+    arrival order -- refused under tunable deterministic = 1 (transpose once with csr_transpose instead).  rowptr may be an un-rebased
+    row sub-range with nnz = its END offset.  x and y must not overlap."""
+    lib = load_library()
+    if m < 0 or n < 0:
+        raise SpmvAccError(f"negative shape ({m}, {n})")
+    _require_tensors(rowptr=rowptr, colindex=colindex, value=value, x=x, y=y)
+    k = max(nnz, 0)
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", k), value=(value, "f64", k), x=(x, "f64", m), y=(y, "f64", n))
+    rc = lib.spmv_acc_csr_spmv_t(alpha, beta, m, n, nnz, _ptr(rowptr), _ptr(colindex), _ptr(value), _ptr(x), _ptr(y))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_spmv_t failed ({rc})")
+
+
+def csr_transpose(m: int, n: int, nnz: int, rowptr, colindex, value=None, want_perm: bool = False):
+    """Stable device transpose (spmv_acc_csr_transpose): returns new GPU tensors (t_rowptr, t_colindex, t_value | None[, perm]) holding the
+    CSR of A^T -- an n x m matrix any entry of this module runs on.  Inside a column the entries keep their source order, so the result is
+    bit for bit a host stable argsort of colindex.  value=None: structure only.  perm[p] = source position of output entry p (for
+    csr_transpose_values).  nnz < 0: read from rowptr[m].  Synchronises; not capturable."""
+    import torch
+
+    lib = load_library()
+    if m < 0 or n < 0:
+        raise SpmvAccError(f"negative shape ({m}, {n})")
+    _require_tensors(rowptr=rowptr, colindex=colindex)
+    if value is not None:
+        _require_tensors(value=value)
+    if nnz < 0:
+        _require(lib, rowptr=(rowptr, "i32", m + 1))
+        nnz = int(rowptr[m].item()) if m > 0 else 0
+        if nnz < 0:
+            raise SpmvAccError(f"rowptr[m] = {nnz}")
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", nnz), value=(value, "f64", nnz))
+    dev = rowptr.device
+    t_rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    t_colindex = torch.empty(nnz, dtype=torch.int32, device=dev)
+    t_value = None if value is None else torch.empty(nnz, dtype=torch.float64, device=dev)
+    perm = torch.empty(nnz, dtype=torch.int32, device=dev) if want_perm else None
+    rc = lib.spmv_acc_csr_transpose(m, n, nnz, _ptr(rowptr), _ptr(colindex), _ptr(value), _ptr(t_rowptr), _ptr(t_colindex), _ptr(t_value),
+                                    _ptr(perm))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_transpose failed ({rc})")
+    return (t_rowptr, t_colindex, t_value, perm) if want_perm else (t_rowptr, t_colindex, t_value)
+
+
+def csr_transpose_values(perm, value, out) -> None:
+    """out[p] = value[perm[p]] (spmv_acc_csr_transpose_values, async on torch's current stream, capturable): the transposed values after an
+    in-place edit of ``value``, with the ``perm`` csr_transpose returned."""
+    lib = load_library()
+    _require_tensors(perm=perm, value=value, out=out)
+    nnz = int(perm.numel())
+    _require(lib, perm=(perm, "i32", nnz), value=(value, "f64", nnz), out=(out, "f64", nnz))
+    rc = lib.spmv_acc_csr_transpose_values(nnz, _ptr(perm), _ptr(value), _ptr(out))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_transpose_values failed ({rc})")
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

@@ -13,6 +13,7 @@
 
 #include "../../include/spmv_acc.h"
 #include "engine.hpp"
+#include "transpose.hpp"
 
 #include <string>
 #include <cstdint>
@@ -194,6 +195,20 @@ void spmv_acc_csr_spmv_oop(int strategy, int trans, double alpha, double beta, i
 int spmv_acc_csr_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz, const int *h_rowptr, const int *d_rowptr,
                       const int *d_colindex, const double *d_value, const double *dX, long long ldx, double *dY, long long ldy) {
   return run_spmm(layout, k, alpha, beta, m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value, dX, ldx, dY, ldy);
+}
+
+int spmv_acc_csr_transpose(int m, int n, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, int *d_t_rowptr,
+                           int *d_t_colindex, double *d_t_value, int *d_perm) {
+  return run_csr_transpose(m, n, nnz, d_rowptr, d_colindex, d_value, d_t_rowptr, d_t_colindex, d_t_value, d_perm);
+}
+
+int spmv_acc_csr_transpose_values(int nnz, const int *d_perm, const double *d_value, double *d_t_value) {
+  return run_csr_transpose_values(nnz, d_perm, d_value, d_t_value);
+}
+
+int spmv_acc_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
+                        const double *dx, double *dy) {
+  return run_csr_spmv_t(alpha, beta, m, n, nnz, d_rowptr, d_colindex, d_value, dx, dy);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
