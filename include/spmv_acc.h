@@ -167,6 +167,60 @@ int spmv_acc_csr_transpose_values(int nnz, const int *d_perm, const double *d_va
 int spmv_acc_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *d_rowptr, const int *d_colindex,
                         const double *d_value, const double *dx, double *dy);
 
+/* ---- assembly, 1: a CSR from unsorted (row, col, value) triples with duplicates, into caller-owned arrays (new) ----------------------
+ * replaces: nothing in the reference; it reads a finished matrix from a file on the host (and its reader keeps duplicates apart).
+ * For callers who BUILD their matrix on the device -- finite-element assembly: a long unsorted list of triples with many duplicates per
+ * position, rebuilt on the same pattern at every time step or Newton iteration.  The m x n CSR this writes is clean: rows sorted by
+ * column, no duplicates, int32 -- every tuned path of the library then sees the matrix in its best form.
+ * Input: nnz_coo triples (d_row, d_col, d_val) in any order, any number of duplicates.  Outputs, all owned by the caller and sized by the
+ * upper bound nnz_coo: d_rowptr (m + 1 ints), d_colindex (nnz_coo ints), d_value (nnz_coo doubles), the map d_order (nnz_coo ints) and
+ * d_start (nnz_coo + 1 ints), and *h_nnz (a host int): the number of distinct positions = the CSR's nnz.  Only the first *h_nnz entries of
+ * d_colindex and d_value and the first *h_nnz + 1 of d_start are written.  d_val and d_value may both be NULL (structure only); d_order
+ * and d_start may both be NULL (the map then lives in the workspace and is dropped); one of a pair without the other is
+ * SPMV_ACC_ERR_BAD_ARGUMENT.
+ * A PURE FUNCTION of the inputs: the triples are ordered by (row, col, input position) with one stable radix sort, d_order[p] = the input
+ * position of the p-th triple in that order; triples with the same (row, col) form a run, run j = positions [d_start[j], d_start[j + 1])
+ * of d_order = CSR entry j, so inside a row the columns ascend strictly.  d_value[j] = the sum of the run's values in ascending input
+ * position, starting from its first value (not from 0.0): runs of up to 64 triples are added by one lane, bitwise a host loop in that
+ * order; longer ones by a wavefront -- lane l adds the values l, l + 64, ... in order, then the 64 partial sums are combined as a balanced
+ * tree over neighbouring lanes (spmv_acc_amd/csrc/coo.hpp states the order in full) -- so that one position hit 10^5 times does not
+ * serialise on a lane.  No atomics: two calls on the same input give the same bits, and tunable "deterministic" changes nothing.
+ * Rows outside [0, m) and columns outside [0, n) are counted before anything is written: if there are any, nothing is written, the
+ * return is SPMV_ACC_ERR_BAD_ARGUMENT and the error string holds their number; a bad index is never turned into an address.
+ * nnz_coo == 0: d_rowptr is set to zeros, *h_nnz = 0, nothing else is touched.  nnz_coo > 0 with m == 0 or n == 0, negative sizes, null
+ * pointers where data is needed: SPMV_ACC_ERR_BAD_ARGUMENT, nothing is launched; m, n or nnz_coo beyond int32 block arithmetic:
+ * SPMV_ACC_ERR_TOO_LARGE.
+ * Runs on the calling thread's library stream and has finished when it returns (it allocates about 16 B per triple of workspace -- 24 B
+ * without the map -- plus the sort's scratch, synchronises, and frees all of it, on the error paths too).  Inside a stream capture it
+ * enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan: hand the CSR to spmv_acc_prepare or any product
+ * entry afterwards.  Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error). */
+int spmv_acc_coo_to_csr(int m, int n, int nnz_coo,
+                        const int *d_row, const int *d_col, const double *d_val,
+                        int *d_rowptr, int *d_colindex, double *d_value,
+                        int *d_order, int *d_start, int *h_nnz);
+
+/* ---- assembly, 2: new values on a known pattern (new; the per-step hot path) -----------------------------------------------------------
+ * replaces: nothing in the reference.  d_value[j] = the sum over p in [d_start[j], d_start[j + 1]) of d_val[d_order[p]] for j < nnz, with
+ * the map (d_order, d_start) and nnz = *h_nnz an earlier spmv_acc_coo_to_csr on the same (row, col) list returned.  The summation orders
+ * are exactly those of the first entry (which runs this kernel for its own values), so re-assembling the same d_val repeats its bits.
+ * One kernel on the calling thread's library stream: asynchronous, no allocation, may be captured into a hipGraph.  The map is the
+ * caller's array here: an entry of d_order outside [0, nnz_coo) is skipped (it counts as +0.0), a d_start interval that reaches outside
+ * [0, nnz_coo] is clamped, and nothing outside the caller's arrays is read or written.  nnz > nnz_coo or a null pointer with nnz > 0:
+ * SPMV_ACC_ERR_BAD_ARGUMENT; nnz == 0: nothing.  The explicit, caller-driven counterpart of spmv_acc_refresh_values (no plan holds a copy
+ * of the caller's values on this route); if a plan does hold a copy of the CSR values the caller rewrites through this entry,
+ * spmv_acc_refresh_values applies as after any in-place edit.  Returns 0 or an spmv_acc_error code.
+ * COST, as measured (MI355X, tools/coo_bench.py, profiles/coo_bench.md; triples = every entry of the stand-in as 1 ... 4 duplicates,
+ * shuffled; the box copied at 6.33 TB/s in the same run): the pass needs 12 B per triple (order + the gathered value) and 12 B per entry
+ * (start + value).  Headline stand-in (101.1 M triples -> 40.45 M entries, settled SpMV 0.143 ms): 2.11 ms = 0.81 TB/s of needed bytes,
+ * 14.8 SpMVs.  FEM class (70.5 M -> 28.2 M, SpMV 0.050 ms): 1.53 ms, 0.77 TB/s, 31 SpMVs.  That is the rate of the memory system, not of
+ * the kernel: after a shuffle every 8-B gather is a 128-B request of its own, and 101.1 M x 128 B / 2.11 ms = 6.1 TB/s is what the box
+ * copies at.  The same pass on triples in the CSR's storage order (contiguous gathers) takes 0.75 / 0.52 ms (2.26 TB/s): a caller who can
+ * emit the triples in a roughly sorted order gets that.  The first entry takes 9.9 / 6.3 ms (70 / 128 SpMVs: once per pattern);
+ * torch.sparse_coo_tensor(...).coalesce() on the same triples takes 34.3 / 23.5 ms for structure and values together, and is the only
+ * form torch offers per step -- the values pass is 16 x / 15 x faster than it. */
+int spmv_acc_coo_to_csr_values(int nnz_coo, int nnz, const int *d_order, const int *d_start,
+                               const double *d_val, double *d_value);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

@@ -41,6 +41,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_shard_destroy", "spmv_acc_rccl_comm_init_all", "spmv_acc_rccl_comm_destroy", "spmv_acc_set_tune_cache",
     "spmv_acc_prepare_beta", "spmv_acc_time_spmv_events", "spmv_acc_refresh_values", "spmv_acc_time_spmv_region", "spmv_acc_query_plan_last_kernel", "spmv_acc_time_spmv_kernels",
     "spmv_acc_csr_spmm", "spmv_acc_csr_transpose", "spmv_acc_csr_transpose_values", "spmv_acc_csr_spmv_t",
+    "spmv_acc_coo_to_csr", "spmv_acc_coo_to_csr_values",
 )
 
 _lib = None
@@ -143,6 +144,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_transpose_values.restype = ci
     lib.spmv_acc_csr_spmv_t.argtypes = [cd, cd, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.spmv_acc_csr_spmv_t.restype = ci
+    lib.spmv_acc_coo_to_csr.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, _c_int_p]
+    lib.spmv_acc_coo_to_csr.restype = ci
+    lib.spmv_acc_coo_to_csr_values.argtypes = [ci, ci, vp, vp, vp, vp]
+    lib.spmv_acc_coo_to_csr_values.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -365,6 +370,59 @@ def csr_transpose_values(perm, value, out) -> None:
     if rc != 0:
         _check(lib)
         raise SpmvAccError(f"csr_transpose_values failed ({rc})")
+
+
+def coo_to_csr(m: int, n: int, row, col, val=None, want_map: bool = False):
+    """Device assembly of an m x n CSR from unsorted triples with duplicates (spmv_acc_coo_to_csr): returns new GPU tensors (rowptr, colindex,
+    value | None[, order, start]).  Rows sorted by column, duplicates summed in ascending input position (bit for bit a host stable sort and,
+    for runs of up to 64 triples, a host loop; longer runs in the wavefront order include/spmv_acc.h documents).  val=None: structure only.
+    order / start: the map csr entry j = triples order[start[j] : start[j + 1]], for coo_to_csr_values.  The C entry writes into arrays of
+    the upper bound len(row); this wrapper allocates those and returns EXACT-size tensors by cloning the used prefixes (colindex, value:
+    nnz; start: nnz + 1; order keeps len(row)), so a matrix with 5 x duplicates does not keep triple-sized arrays alive.  Synchronises; not
+    capturable."""
+    import torch
+
+    lib = load_library()
+    if m < 0 or n < 0:
+        raise SpmvAccError(f"negative shape ({m}, {n})")
+    _require_tensors(row=row, col=col)
+    if val is not None:
+        _require_tensors(val=val)
+    nnz_coo = int(row.numel())
+    if int(col.numel()) > nnz_coo or (val is not None and int(val.numel()) > nnz_coo):  # (fewer: the "elements" check below)
+        raise SpmvAccError(f"row holds {nnz_coo} elements, col and val must hold as many")
+    _require(lib, row=(row, "i32", nnz_coo), col=(col, "i32", nnz_coo), val=(val, "f64", nnz_coo))
+    dev = row.device
+    rowptr = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    colindex = torch.empty(nnz_coo, dtype=torch.int32, device=dev)
+    value = None if val is None else torch.empty(nnz_coo, dtype=torch.float64, device=dev)
+    order = torch.empty(nnz_coo, dtype=torch.int32, device=dev) if want_map else None
+    start = (torch.empty if nnz_coo else torch.zeros)(nnz_coo + 1, dtype=torch.int32, device=dev) if want_map else None  # (no triples: start = [0])
+    h_nnz = ctypes.c_int(0)
+    args = (row, col, val, rowptr, colindex, value, order, start) if nnz_coo else (None, None, None, rowptr, None, None, None, None)
+    rc = lib.spmv_acc_coo_to_csr(m, n, nnz_coo, *(_ptr(t) for t in args), ctypes.byref(h_nnz))  # (empty tensors have null pointers: not passed)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"coo_to_csr failed ({rc})")
+    nnz = int(h_nnz.value)
+    out = (rowptr, colindex[:nnz].clone(), None if value is None else value[:nnz].clone())
+    return out + (order, start[:nnz + 1].clone()) if want_map else out
+
+
+def coo_to_csr_values(order, start, val, out) -> None:
+    """out[j] = sum of val[order[start[j] : start[j + 1]]] (spmv_acc_coo_to_csr_values, async on torch's current stream, capturable): the CSR
+    values of new triple values on a known pattern, with the map coo_to_csr(..., want_map=True) returned; len(out) = len(start) - 1 = nnz.
+    The same summation orders as coo_to_csr, so the same ``val`` gives the same bits."""
+    lib = load_library()
+    _require_tensors(order=order, start=start, val=val, out=out)
+    nnz_coo, nnz = int(order.numel()), int(start.numel()) - 1
+    if nnz < 0:
+        raise SpmvAccError("start: 0 elements, the map of an empty matrix still holds one")
+    _require(lib, order=(order, "i32", nnz_coo), start=(start, "i32", nnz + 1), val=(val, "f64", nnz_coo), out=(out, "f64", nnz))
+    rc = lib.spmv_acc_coo_to_csr_values(nnz_coo, nnz, _ptr(order), _ptr(start), _ptr(val), _ptr(out))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"coo_to_csr_values failed ({rc})")
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

@@ -14,6 +14,7 @@
 #include "../../include/spmv_acc.h"
 #include "engine.hpp"
 #include "transpose.hpp"
+#include "coo.hpp"
 
 #include <string>
 #include <cstdint>
@@ -209,6 +210,15 @@ int spmv_acc_csr_transpose_values(int nnz, const int *d_perm, const double *d_va
 int spmv_acc_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
                         const double *dx, double *dy) {
   return run_csr_spmv_t(alpha, beta, m, n, nnz, d_rowptr, d_colindex, d_value, dx, dy);
+}
+
+int spmv_acc_coo_to_csr(int m, int n, int nnz_coo, const int *d_row, const int *d_col, const double *d_val, int *d_rowptr, int *d_colindex,
+                        double *d_value, int *d_order, int *d_start, int *h_nnz) {
+  return run_coo_to_csr(m, n, nnz_coo, d_row, d_col, d_val, d_rowptr, d_colindex, d_value, d_order, d_start, h_nnz);
+}
+
+int spmv_acc_coo_to_csr_values(int nnz_coo, int nnz, const int *d_order, const int *d_start, const double *d_val, double *d_value) {
+  return run_coo_to_csr_values(nnz_coo, nnz, d_order, d_start, d_val, d_value);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,

@@ -107,6 +107,25 @@ def banded_csr(m, offsets=(-4, -3, -2, -1, 0, 1, 2, 3), first_row=0, total_rows=
     return rowptr.astype(np.int32), cols[ok].astype(np.int32), vals[ok].astype(np.float64)
 
 
+def fem_quads_coo(nx, ny, seed):
+    """The unsorted triple list of a bilinear-quad assembly on an nx x ny element grid: (row, col, val) for the (nx + 1) * (ny + 1)-node
+    matrix, element by element, 16 triples per element (its 4 x 4 local matrix, random values), nothing merged.  A position is hit once
+    (corner pairs across an element), twice (pairs on an interior edge) or four times (an interior node's diagonal)."""
+    rng = np.random.default_rng(seed)
+    ex, ey = np.meshgrid(np.arange(nx, dtype=np.int64), np.arange(ny, dtype=np.int64), indexing="ij")
+    n0 = (ex * (ny + 1) + ey).reshape(-1)
+    nodes = np.stack([n0, n0 + ny + 1, n0 + ny + 2, n0 + 1], axis=1)  # counter-clockwise corners of every element
+    row = np.repeat(nodes, 4, axis=1).reshape(-1).astype(np.int32)
+    col = np.tile(nodes, (1, 4)).reshape(-1).astype(np.int32)
+    return row, col, rng.uniform(-1.0, 1.0, size=row.size)
+
+
+def shuffle_coo(row, col, val, seed):
+    """The same triples in a random order (one permutation for the three arrays)."""
+    perm = np.random.default_rng(seed).permutation(len(row))
+    return row[perm], col[perm], (None if val is None else val[perm])
+
+
 def reference_rand_grid(n, rng):
     """Vectors on the reference's 100-point grid: -1 + 2*(k % 100)/101 (cli/utils.hpp:46-49), with k
     from a seeded numpy generator instead of libc rand()."""
