@@ -16,6 +16,7 @@ import pytest
 
 import spmv_acc_amd
 from spmv_acc_amd import synth
+from special_values import MEASUREMENT_SWITCHES
 
 pytestmark = pytest.mark.gpu
 
@@ -685,32 +686,7 @@ def test_measurement_switches_keep_parity(torch_dev, oracle, hiplib):
     drp, dci, dv, dx = (dev(torch, a) for a in (rowptr, cols, vals, x))
     nnz = int(rowptr[-1])
     ref = oracle.host_spmv(1.0, 1.0, rowptr, cols, vals, x, y0)
-    variants = [("flat", {"flat_npt": 4}), ("flat", {"flat_npt": 16}), ("flat", {"xcd_chunk": 0}), ("flat", {"xcd_chunk": 5}),
-                ("line_enhance", {"xcd_chunk": 0}),
-                ("line_enhance", {"xcd_chunk": 64}), ("line_enhance", {"rowblock_guard": 0}),
-                ("line_enhance", {"rowblock_vec": 8}), ("line_enhance", {"rowblock_target": 600}),
-                ("adaptive_plus", {"plus_host_analysis": 1}), ("adaptive_plus", {"xcd_chunk": 0}), ("adaptive_plus", {"xcd_chunk": 3}),
-                # round 2: row digest on / off, vector-row forms, flat's stream-first staging and tile sizes, 16-bit columns
-                ("line_enhance", {"rowlen": 1, "rowblock_guard": 0}), ("line_enhance", {"rowlen": 0, "rowblock_guard": 0}),
-                ("line_enhance", {"rowlen": 1, "rowblock_vec": 4, "rowblock_guard": 0}), ("line_enhance", {"rowlen": 1, "rowblock_vec": 64, "rowblock_guard": 0}),
-                ("line", {"rowlen": 1, "rowblock_target": 700, "rowblock_guard": 0}),
-                ("vector_row", {"vector_tile": 0}), ("vector_row", {"vector_tile": 1, "rowblock_guard": 0}), ("light", {"vector_tile": 1, "rowblock_guard": 0}),
-                ("adaptive", {"adaptive_timed": 0, "adaptive_split": 1, "vector_tile": 1}), ("adaptive", {"adaptive_timed": 0, "adaptive_split": 1, "vector_tile": 0}),
-                ("flat", {"flat_early": 1, "flat_npt": 8}), ("flat", {"flat_early": 1, "flat_npt": 4}), ("flat", {"flat_early": 0, "flat_npt": 4}),
-                ("flat", {"flat_early": 1, "flat_npt": 16, "flat_finish": 0}), ("flat", {"col16": 1}), ("flat", {"col16": 1, "flat_finish": 0}),
-                # walking direction and cacheable grid ends (speed only)
-                ("flat", {"zigzag": 0}), ("line_enhance", {"zigzag": 0}), ("adaptive_plus", {"zigzag": 0}), ("vector_row", {"zigzag": 0}),
-                ("line_enhance", {"cache_ends_mb": 0, "stream_plain": 0}), ("line_enhance", {"cache_ends_mb": 1, "stream_plain": 0}),
-                ("flat", {"cache_ends_mb": 1, "stream_plain": 0}), ("flat", {"cache_ends_mb": 4000, "stream_plain": 0}),
-                # the segmented-scan reduction of a flat tile (the reference's FLAT_SEGMENT_SUM_REDUCE)
-                ("flat", {"flat_reduce": 1}), ("flat", {"flat_reduce": 1, "flat_finish": 0}), ("flat", {"flat_reduce": 1, "flat_finish": 1, "stream_plain": 1}),
-                ("flat", {"flat_reduce": 1, "flat_npt": 4}),
-                # gather hints (cold gathers non-temporal): forced on, tiny and huge hot sets
-                ("adaptive_plus", {"gather_hint": 1}), ("adaptive_plus", {"gather_hint": 1, "hint_budget_kb": 1}),
-                ("adaptive_plus", {"gather_hint": 1, "hint_budget_kb": 100000}), ("flat", {"gather_hint": 1, "flat_npt": 8, "flat_early": 0}),
-                ("flat", {"gather_hint": 1, "hint_budget_kb": 8, "flat_npt": 8, "flat_early": 0, "flat_finish": 0}),
-                ("adaptive", {"gather_hint": 1, "hint_budget_kb": 16}), ("line_enhance", {"gather_hint": 1, "hint_budget_kb": 16}),
-                ("line_enhance", {"gather_hint": 1, "rowblock_guard": 0, "rowlen": 1}), ("default", {"gather_hint": 1, "hint_budget_kb": 1})]
+    variants = MEASUREMENT_SWITCHES  # (tests/special_values.py: tests/test_gpu_special_values.py runs the same inventory on poisoned data)
     try:
         for strat, knobs in variants:
             hiplib.spmv_acc_reset_tunables()
@@ -1269,7 +1245,8 @@ def test_benchmark_flat_copy_surface(torch_dev, oracle, tmp_path):
 def test_nan_stays_in_its_row(torch_dev, oracle):
     """A NaN (or Inf) in one matrix value must reach exactly the rows that hold it: the kernels load whole 16-byte groups and
     staged tiles that contain neighbouring rows' elements, and mask or ignore the foreign ones rather than multiply them by zero.
-    Also beta = 0 must not read y (BLAS convention): a y full of NaN comes back finite."""
+    Also beta = 0 must not read y (BLAS convention): a y full of NaN comes back finite.
+    (Non-finite x, every pinned kernel form, the newer entries and subnormals: tests/test_gpu_special_values.py.)"""
     torch = torch_dev
     rng = np.random.default_rng(77)
     lens = rng.integers(1, 9, 20000)
