@@ -221,6 +221,80 @@ int spmv_acc_coo_to_csr(int m, int n, int nnz_coo,
 int spmv_acc_coo_to_csr_values(int nnz_coo, int nnz, const int *d_order, const int *d_start,
                                const double *d_val, double *d_value);
 
+/* ---- sparse product C = A * B, 1: the number of scalar products (new) -----------------------------------------------------------------
+ * replaces: nothing in the reference; it multiplies a matrix by a vector.
+ * A is m x k, B is k x n, both CSR, int32, fp64 and rebased (rowptr[0] == 0); rows need NOT be sorted and an input may hold duplicate
+ * positions, which act as separate entries.  *h_nprod (a host 64-bit integer) = the number of scalar products a_ik * b_kj = the sum over
+ * A's non-zeros of the length of B's row a_colindex[q] = the size of the expansion = the upper bound on nnz(C) by which the caller sizes
+ * the arrays of the next entry.  One range census of A's columns, one count pass and one reduction on the calling thread's library stream;
+ * synchronises; inside a stream capture it enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  nnz_a < 0: a_rowptr[m] is read from
+ * the device; a given nnz_a must be a_rowptr[m].  A column of A outside [0, k) is never turned into an address: SPMV_ACC_ERR_BAD_ARGUMENT
+ * with their number in the error string.  A count beyond INT_MAX - 2^16 is still returned in *h_nprod, with SPMV_ACC_ERR_TOO_LARGE: the
+ * next entry cannot take it; rows of C are independent, so multiply row ranges of A.  Makes and touches no plan. */
+int spmv_acc_csr_spgemm_products(int m, int k, int nnz_a, const int *d_a_rowptr, const int *d_a_colindex,
+                                 const int *d_b_rowptr, long long *h_nprod);
+
+/* ---- sparse product C = A * B, 2: structure, map and first values, into caller-owned arrays (new) --------------------------------------
+ * replaces: nothing in the reference.  For callers who form Galerkin products R * A * P, A^T * A (with spmv_acc_csr_transpose), pattern
+ * powers or Schur-complement pieces on the device and rebuild them on the same pattern at every time step or Newton iteration.  The m x n
+ * CSR this writes is clean -- every row strictly ascending in column, int32 -- whatever the inputs looked like.  An entry exists wherever
+ * a product exists; a sum of 0.0 is kept.
+ * Outputs, all owned by the caller and sized by nprod = the count of the first entry: d_c_rowptr (m + 1 ints), d_c_colindex (nprod ints),
+ * d_c_value (nprod doubles), the map d_pa, d_pb (nprod ints each) and d_start (nprod + 1 ints), and *h_nnz (a host int) = nnz(C).  Only
+ * the first *h_nnz entries of d_c_colindex / d_c_value and the first *h_nnz + 1 of d_start are written.  d_a_value, d_b_value, d_c_value
+ * all NULL: structure only; d_pa, d_pb, d_start all NULL: the map lives in the workspace and is dropped; any other mix of NULLs inside
+ * a group is SPMV_ACC_ERR_BAD_ARGUMENT.  nprod must equal the entry's own count (it guards an under-sized allocation), else
+ * SPMV_ACC_ERR_BAD_ARGUMENT with the count in the error string.
+ * A PURE FUNCTION of the inputs, by expand - sort - compress.  EXPANSION ORDER: product e enumerates A's non-zeros q in storage order
+ * and, for each, the entries t of B's row a_colindex[q] in storage order: e = off[q] + (t - b_rowptr[a_colindex[q]]), off = the exclusive
+ * scan of those rows' lengths; its key is (row of q, b_colindex[t]).  ONE stable radix sort of (key, e), the assembly's: products with
+ * equal (i, j) then form a run in ascending e; run j is C entry j and covers sorted positions [d_start[j], d_start[j + 1]); d_pa[p] and
+ * d_pb[p] are the positions of the two factors of sorted product p in A's and B's arrays.  VALUES: d_c_value[j] = the sum of the run's
+ * products a_value[d_pa[p]] * b_value[d_pb[p]], each ROUNDED to fp64 before it is added (no fused multiply-add), in exactly the
+ * assembly's summation order (spmv_acc_coo_to_csr above, spmv_acc_amd/csrc/coo.hpp): runs of up to 64 products by one lane starting from
+ * the first product, bitwise a host loop; longer ones by a wavefront -- strided partial sums, then the balanced tree.  No atomics: two
+ * calls on the same inputs give the same bits, and tunable "deterministic" changes nothing.  The values come from the next entry's kernel.
+ * Columns of A outside [0, k) and of B outside [0, n) are counted before anything reads through them: if there are any, nothing is
+ * written, the return is SPMV_ACC_ERR_BAD_ARGUMENT and the error string holds their numbers.  a_rowptr[0] != 0, b_rowptr[0] != 0, or a
+ * given nnz_a / nnz_b that is not rowptr[last]: SPMV_ACC_ERR_BAD_ARGUMENT (nnz_a / nnz_b < 0: read from the device).  Null pointers where
+ * data is needed, negative sizes: SPMV_ACC_ERR_BAD_ARGUMENT, nothing is launched.  No products (no non-zeros, or A only meets empty rows
+ * of B; nprod == 0): d_c_rowptr is set to zeros, *h_nnz = 0, nothing else is touched.  m, k, n, nnz_a, nnz_b or the product count beyond
+ * INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE with the count in the error string; rows of C are independent, so multiply row ranges of A.
+ * Runs on the calling thread's library stream and has finished when it returns.  WORKSPACE, one allocation, freed on every path: 16 B per
+ * product (the packed keys before and after the sort; no factor position is kept through the sort, the map is recomputed from the sorted
+ * order) -- 28 B without the map -- plus 20 B per non-zero of A and the sort's scratch: the assembly's class.  Inside a stream capture it
+ * enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan: hand C to spmv_acc_prepare or any product entry
+ * afterwards.  Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST, as measured (MI355X, tools/spgemm_bench.py, profiles/spgemm_bench.md; the box copied at 6.41 TB/s in the same run): the time follows
+ * the PRODUCT count, not nnz(C).  Headline stand-in, A^T * A (201.3 M products -> 112.7 M entries; settled SpMV on A 0.142 ms): 21.4 ms =
+ * 150 SpMVs.  FEM class, A * A (868.7 M products -> 111.5 M entries, 7.8 products per entry; SpMV 0.059 ms): 81.6 ms = 1 393 SpMVs.
+ * Galerkin-shaped R * (A * P) with an 8 : 1 aggregation, both products together: 9.0 ms (59.4 M products, 63 SpMVs) and 5.4 ms (33.9 M, 91
+ * SpMVs).  torch.sparse CSR @ CSR (rocSPARSE, hash accumulation: structure and values in one step, no kept map, sums in no stated order)
+ * takes 5.1 / 6.4 / 2.2 / 1.1 ms on the four: 4 x to 13 x FASTER than this entry for a product formed once -- most where many products
+ * fall on one entry.  This entry pays per scalar product for being a pure function of its inputs and for the map of the next entry. */
+int spmv_acc_csr_spgemm(int m, int k, int n,
+                        int nnz_a, const int *d_a_rowptr, const int *d_a_colindex, const double *d_a_value,
+                        int nnz_b, const int *d_b_rowptr, const int *d_b_colindex, const double *d_b_value,
+                        int nprod, int *d_c_rowptr, int *d_c_colindex, double *d_c_value,
+                        int *d_pa, int *d_pb, int *d_start, int *h_nnz);
+
+/* ---- sparse product C = A * B, 3: new values of A and / or B on a known pattern (new; the per-step hot path) ----------------------------
+ * replaces: nothing in the reference.  d_c_value[j] = the sum over p in [d_start[j], d_start[j + 1]) of d_a_value[d_pa[p]] *
+ * d_b_value[d_pb[p]] for j < nnz_c, with the map (d_pa, d_pb, d_start), nprod and nnz_c = *h_nnz of an earlier spmv_acc_csr_spgemm on
+ * the same two patterns.  Rounding and summation order are exactly the first entry's (which runs this kernel for its own values), so the
+ * same values repeat its bits.  One kernel on the calling thread's library stream: asynchronous, no allocation, may be captured into a
+ * hipGraph.  The map is the caller's array here: a d_start interval that reaches outside [0, nprod] is clamped; an entry of d_pa / d_pb
+ * outside A's / B's value arrays CANNOT be checked (their lengths are not passed), so THE MAP MUST COME FROM THE FIRST ENTRY, unedited.
+ * nnz_c > nprod or a null pointer with nnz_c > 0: SPMV_ACC_ERR_BAD_ARGUMENT; nnz_c == 0: nothing.  It streams 8 B of map per product
+ * and 12 B per entry and gathers 16 B per product.  Returns 0 or an spmv_acc_error code.
+ * COST, as measured (same run): headline stand-in A^T * A 1.85 ms = 3.34 TB/s of those needed bytes, 13 SpMVs (torch's whole product:
+ * 5.1 ms); Galerkin-shaped R * (A * P) 0.98 ms (headline, 1.77 TB/s, 7 SpMVs; torch 2.2 ms) and 0.60 ms (FEM class, 1.50 TB/s, 10 SpMVs;
+ * torch 1.1 ms); FEM class A * A, 868.7 M products on 111.5 M entries: 14.1 ms = 1.57 TB/s, 241 SpMVs -- SLOWER than torch's whole product
+ * (6.4 ms): with 7.8 products per entry the 24 B streamed and gathered per product outweigh a hash accumulator's work per entry.  Keep the
+ * map where a few products fall on an entry (Galerkin products, A^T * A of short rows); on dense-ish squares it does not pay. */
+int spmv_acc_csr_spgemm_values(int nprod, int nnz_c, const int *d_pa, const int *d_pb, const int *d_start,
+                               const double *d_a_value, const double *d_b_value, double *d_c_value);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

@@ -42,6 +42,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_prepare_beta", "spmv_acc_time_spmv_events", "spmv_acc_refresh_values", "spmv_acc_time_spmv_region", "spmv_acc_query_plan_last_kernel", "spmv_acc_time_spmv_kernels",
     "spmv_acc_csr_spmm", "spmv_acc_csr_transpose", "spmv_acc_csr_transpose_values", "spmv_acc_csr_spmv_t",
     "spmv_acc_coo_to_csr", "spmv_acc_coo_to_csr_values",
+    "spmv_acc_csr_spgemm_products", "spmv_acc_csr_spgemm", "spmv_acc_csr_spgemm_values",
 )
 
 _lib = None
@@ -148,6 +149,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_coo_to_csr.restype = ci
     lib.spmv_acc_coo_to_csr_values.argtypes = [ci, ci, vp, vp, vp, vp]
     lib.spmv_acc_coo_to_csr_values.restype = ci
+    lib.spmv_acc_csr_spgemm_products.argtypes = [ci, ci, ci, vp, vp, vp, ctypes.POINTER(ctypes.c_longlong)]
+    lib.spmv_acc_csr_spgemm_products.restype = ci
+    lib.spmv_acc_csr_spgemm.argtypes = [ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, _c_int_p]
+    lib.spmv_acc_csr_spgemm.restype = ci
+    lib.spmv_acc_csr_spgemm_values.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
+    lib.spmv_acc_csr_spgemm_values.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -423,6 +430,95 @@ def coo_to_csr_values(order, start, val, out) -> None:
     if rc != 0:
         _check(lib)
         raise SpmvAccError(f"coo_to_csr_values failed ({rc})")
+
+
+def _spgemm_args(lib, m, k, n, a_rowptr, a_colindex, a_value, b_rowptr, b_colindex, b_value):
+    """The checks the two structural SpGEMM wrappers share; returns (nnz_a, nnz_b) = the lengths of the index arrays."""
+    if m < 0 or k < 0 or n < 0:
+        raise SpmvAccError(f"negative shape ({m}, {k}) * ({k}, {n})")
+    _require_tensors(a_rowptr=a_rowptr, a_colindex=a_colindex, b_rowptr=b_rowptr)
+    named = dict(a_rowptr=(a_rowptr, "i32", m + 1), a_colindex=(a_colindex, "i32", 0), b_rowptr=(b_rowptr, "i32", k + 1))
+    nnz_a, nnz_b = int(a_colindex.numel()), -1
+    if b_colindex is not None:
+        _require_tensors(b_colindex=b_colindex)
+        nnz_b = int(b_colindex.numel())
+        named["b_colindex"] = (b_colindex, "i32", 0)
+    if (a_value is None) != (b_value is None):
+        raise SpmvAccError("a_value and b_value must both be given or both be None (structure only)")
+    if a_value is not None:
+        _require_tensors(a_value=a_value, b_value=b_value)
+        if int(a_value.numel()) > nnz_a or int(b_value.numel()) > nnz_b:  # (fewer: the "elements" check below)
+            raise SpmvAccError(f"a_colindex / b_colindex hold {nnz_a} / {nnz_b} elements, a_value / b_value must hold as many")
+        named.update(a_value=(a_value, "f64", nnz_a), b_value=(b_value, "f64", nnz_b))
+    _require(lib, **named)
+    return nnz_a, nnz_b
+
+
+def csr_spgemm_products(m: int, k: int, a_rowptr, a_colindex, b_rowptr) -> int:
+    """The number of scalar products a_ik * b_kj of C = A * B (spmv_acc_csr_spgemm_products): the expansion's size and the upper bound on
+    nnz(C).  A is m x k, B is k x n, rebased CSR; len(a_colindex) must be a_rowptr[m] (slice a longer array).  Synchronises; not
+    capturable.  Raises SpmvAccError (with the count in its message) when the count is beyond what csr_spgemm takes."""
+    lib = load_library()
+    nnz_a, _ = _spgemm_args(lib, m, k, 0, a_rowptr, a_colindex, None, b_rowptr, None, None)
+    h = ctypes.c_longlong(0)
+    rc = lib.spmv_acc_csr_spgemm_products(m, k, nnz_a, _ptr(a_rowptr), _ptr(a_colindex) if nnz_a else 0, _ptr(b_rowptr), ctypes.byref(h))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_spgemm_products failed ({rc})")
+    return int(h.value)
+
+
+def csr_spgemm(m: int, k: int, n: int, a_rowptr, a_colindex, a_value, b_rowptr, b_colindex, b_value, want_map: bool = False):
+    """Device sparse product C = A * B (spmv_acc_csr_spgemm), A m x k and B k x n in rebased CSR whose rows need not be sorted: returns
+    new GPU tensors (rowptr, colindex, value | None[, pa, pb, start]).  Rows of C strictly ascending in column; every value the sum of its
+    products a[pa[p]] * b[pb[p]], p in [start[j], start[j + 1]), each rounded before it is added, in the order include/spmv_acc.h
+    documents -- a pure function of the inputs, bit for bit.  a_value = b_value = None: structure only.  pa / pb / start: the map for
+    csr_spgemm_values.  len(a_colindex) / len(b_colindex) must be a_rowptr[m] / b_rowptr[k].  This wrapper queries the product count,
+    allocates arrays of that upper bound and returns EXACT-size tensors by cloning the used prefixes (colindex, value: nnz(C); start:
+    nnz(C) + 1; pa and pb keep the product count).  Synchronises; not capturable."""
+    import torch
+
+    lib = load_library()
+    _require_tensors(b_colindex=b_colindex)
+    nnz_a, nnz_b = _spgemm_args(lib, m, k, n, a_rowptr, a_colindex, a_value, b_rowptr, b_colindex, b_value)
+    nprod = csr_spgemm_products(m, k, a_rowptr, a_colindex, b_rowptr)
+    dev = a_rowptr.device
+    rowptr = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    colindex = torch.empty(nprod, dtype=torch.int32, device=dev)
+    value = None if a_value is None else torch.empty(nprod, dtype=torch.float64, device=dev)
+    pa = torch.empty(nprod, dtype=torch.int32, device=dev) if want_map else None
+    pb = torch.empty(nprod, dtype=torch.int32, device=dev) if want_map else None
+    start = (torch.empty if nprod else torch.zeros)(nprod + 1, dtype=torch.int32, device=dev) if want_map else None  # (no products: start = [0])
+    h_nnz = ctypes.c_int(0)
+    ins = tuple(_ptr(t) if t is not None and t.numel() and (nprod or i % 2 == 0) else 0  # (empty tensors: null pointers; no products: no values)
+                for i, t in enumerate((a_colindex, a_value, b_colindex, b_value)))
+    outs = tuple(_ptr(t) if nprod else 0 for t in (colindex, value, pa, pb, start))
+    rc = lib.spmv_acc_csr_spgemm(m, k, n, nnz_a, _ptr(a_rowptr), ins[0], ins[1], nnz_b, _ptr(b_rowptr), ins[2], ins[3], nprod, _ptr(rowptr),
+                                 *outs, ctypes.byref(h_nnz))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_spgemm failed ({rc})")
+    nnz = int(h_nnz.value)
+    out = (rowptr, colindex[:nnz].clone(), None if value is None else value[:nnz].clone())
+    return out + (pa, pb, start[:nnz + 1].clone()) if want_map else out
+
+
+def csr_spgemm_values(pa, pb, start, a_value, b_value, out) -> None:
+    """out[j] = sum of a_value[pa[p]] * b_value[pb[p]] over p in [start[j], start[j + 1]) (spmv_acc_csr_spgemm_values, async on torch's
+    current stream, capturable): the values of C for new values of A and / or B on known patterns, with the map csr_spgemm(...,
+    want_map=True) returned; len(out) = len(start) - 1 = nnz(C).  The same rounding and summation order as csr_spgemm, so the same values
+    give the same bits.  pa / pb cannot be checked against the value arrays: pass the map as csr_spgemm returned it."""
+    lib = load_library()
+    _require_tensors(pa=pa, pb=pb, start=start, a_value=a_value, b_value=b_value, out=out)
+    nprod, nnz_c = int(pa.numel()), int(start.numel()) - 1
+    if nnz_c < 0:
+        raise SpmvAccError("start: 0 elements, the map of an empty product still holds one")
+    _require(lib, pa=(pa, "i32", nprod), pb=(pb, "i32", nprod), start=(start, "i32", nnz_c + 1), a_value=(a_value, "f64", 1 if nprod else 0),
+             b_value=(b_value, "f64", 1 if nprod else 0), out=(out, "f64", nnz_c))
+    rc = lib.spmv_acc_csr_spgemm_values(nprod, nnz_c, _ptr(pa), _ptr(pb), _ptr(start), _ptr(a_value), _ptr(b_value), _ptr(out))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_spgemm_values failed ({rc})")
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

@@ -15,6 +15,7 @@
 #include "engine.hpp"
 #include "transpose.hpp"
 #include "coo.hpp"
+#include "spgemm.hpp"
 
 #include <string>
 #include <cstdint>
@@ -219,6 +220,23 @@ int spmv_acc_coo_to_csr(int m, int n, int nnz_coo, const int *d_row, const int *
 
 int spmv_acc_coo_to_csr_values(int nnz_coo, int nnz, const int *d_order, const int *d_start, const double *d_val, double *d_value) {
   return run_coo_to_csr_values(nnz_coo, nnz, d_order, d_start, d_val, d_value);
+}
+
+int spmv_acc_csr_spgemm_products(int m, int k, int nnz_a, const int *d_a_rowptr, const int *d_a_colindex, const int *d_b_rowptr,
+                                 long long *h_nprod) {
+  return run_csr_spgemm_products(m, k, nnz_a, d_a_rowptr, d_a_colindex, d_b_rowptr, h_nprod);
+}
+
+int spmv_acc_csr_spgemm(int m, int k, int n, int nnz_a, const int *d_a_rowptr, const int *d_a_colindex, const double *d_a_value, int nnz_b,
+                        const int *d_b_rowptr, const int *d_b_colindex, const double *d_b_value, int nprod, int *d_c_rowptr, int *d_c_colindex,
+                        double *d_c_value, int *d_pa, int *d_pb, int *d_start, int *h_nnz) {
+  return run_csr_spgemm(m, k, n, nnz_a, d_a_rowptr, d_a_colindex, d_a_value, nnz_b, d_b_rowptr, d_b_colindex, d_b_value, nprod, d_c_rowptr,
+                        d_c_colindex, d_c_value, d_pa, d_pb, d_start, h_nnz);
+}
+
+int spmv_acc_csr_spgemm_values(int nprod, int nnz_c, const int *d_pa, const int *d_pb, const int *d_start, const double *d_a_value,
+                               const double *d_b_value, double *d_c_value) {
+  return run_csr_spgemm_values(nprod, nnz_c, d_pa, d_pb, d_start, d_a_value, d_b_value, d_c_value);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
