@@ -295,6 +295,74 @@ int spmv_acc_csr_spgemm(int m, int k, int n,
 int spmv_acc_csr_spgemm_values(int nprod, int nnz_c, const int *d_pa, const int *d_pb, const int *d_start,
                                const double *d_a_value, const double *d_b_value, double *d_c_value);
 
+/* ---- sparse add C = alpha * A + beta * B, 1: structure, map and first values, into caller-owned arrays (new) ----------------------------
+ * replaces: nothing in the reference; it multiplies a matrix by a vector.  For callers who form M + dt * K, shifts A + sigma * I,
+ * symmetrisations A + A^T (with spmv_acc_csr_transpose) or Galerkin corrections R * A * P + D on the device and rebuild them on the same
+ * patterns at every step.
+ * INPUTS: A and B are both m x n, CSR, int32, fp64, rebased (rowptr[0] == 0), and every row is STRICTLY ASCENDING in column -- sorted, no
+ * duplicate -- which is what spmv_acc_coo_to_csr, spmv_acc_csr_transpose and spmv_acc_csr_spgemm write.  Explicit zeros are ordinary
+ * entries.  nnz_a / nnz_b must be rowptr[m], or negative: read from the device.
+ * THE RESULT IS UNIQUE (no implementation choice can change a bit of it).  PATTERN: row i of C is the sorted union of row i of A and row
+ * i of B; nothing is pruned, an entry whose value cancels to 0.0 stays; *h_nnz (a host int) = nnz(C) <= nnz_a + nnz_b.  MAP: d_ia[j] =
+ * the position of C entry j in A's arrays, or -1 where A has no entry there; d_ib[j] likewise for B; at least one of the two is >= 0.
+ * VALUES: with ta = alpha * a_value[ia[j]] and tb = beta * b_value[ib[j]], each ROUNDED to fp64 (no fused multiply-add): both present:
+ * c_value[j] = ta + tb; only A present: ta; only B present: tb.  No implicit + 0.0: an A-only -0.0 with alpha == 1 stays -0.0; alpha
+ * == 0 is not special-cased, 0 * Inf = NaN propagates; the pattern is the union whatever alpha and beta are.  The values come from the
+ * next entry's kernel, so they are bit-equal to what it gives on the returned map.
+ * OUTPUTS, all owned by the caller: d_c_rowptr (m + 1 ints); d_c_colindex, d_c_value, d_ia, d_ib sized nnz_a + nnz_b (no count entry is
+ * needed); only their first *h_nnz elements are written.  d_a_value, d_b_value, d_c_value all NULL: structure only; d_ia, d_ib both
+ * NULL: no map is returned (with values, a copy lives in the workspace and is dropped); any other mix of NULLs inside a group is
+ * SPMV_ACC_ERR_BAD_ARGUMENT (a matrix without non-zeros still passes a non-null value pointer; it is not read).  d_c_value must not
+ * overlap d_a_value or d_b_value, and no output may overlap an input.
+ * CHECKS.  On the host, before the device is touched: negative m or n, null pointers where data is needed: SPMV_ACC_ERR_BAD_ARGUMENT;
+ * m, n, nnz_a, nnz_b or nnz_a + nnz_b beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE -- rows of C are independent, so add row ranges of A
+ * and B.  On the device, each SPMV_ACC_ERR_BAD_ARGUMENT: rowptr[0] != 0; a given nnz_a / nnz_b that is not rowptr[m]; and ONE CENSUS of
+ * both matrices before anything reads through an index, counting (a) columns outside [0, n), (b) positions inside a row whose column
+ * does not exceed its predecessor's, (c) rows whose rowptr extent descends or leaves [0, nnz]: if any count is non-zero nothing was
+ * written and the error string holds the three counts per matrix (for (b): spmv_acc_coo_to_csr sorts and merges such a matrix).  An
+ * empty A, an empty B, both empty or m == 0 succeed: C is the other matrix scaled, or d_c_rowptr all zeros (then nothing else is touched
+ * and nothing is allocated).
+ * Runs on the calling thread's library stream and has finished when it returns.  No sort: every entry's place in C is a rank each
+ * non-zero computes on its own (one binary search in the other matrix' row; spmv_acc_amd/csrc/csr_add.hpp), all passes are cut by
+ * non-zeros, none by rows, and there is no atomic: two calls on the same inputs give the same bits, tunable "deterministic" changes
+ * nothing.  WORKSPACE, one allocation, freed on every path: 8 B per non-zero of A, 96 KiB of census counts and the scan's scratch, plus
+ * 8 B per possible entry when values are wanted without a map.  Inside a stream capture it enqueues nothing and returns
+ * SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan: hand C to spmv_acc_prepare or any product entry afterwards.  Returns 0 or an
+ * spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST, as measured (MI355X, tools/csr_add_bench.py, profiles/csr_add_bench.md; the box copied at 6.59 TB/s in the same run; stand-ins made
+ * canonical by spmv_acc_coo_to_csr first).  Headline stand-in (settled SpMV on A 0.145 ms): M + dt K on one pattern, 40.5 M + 40.5 M ->
+ * 40.5 M entries, 6.2 ms = 43 SpMVs; A + sigma I, 40.5 M + 7.6 M -> 48.0 M, 5.1 ms = 35 SpMVs; torch.add on sparse-CSR tensors (structure
+ * and values in one step, no kept map) takes 8.3 / 9.8 ms there.  FEM class (SpMV 0.049 ms): A + A^T, 28.2 M + 28.2 M -> 35.1 M, 4.1 ms =
+ * 84 SpMVs; M + dt K 3.4 ms; A + sigma I 2.5 ms -- torch.add takes 1.57 / 1.20 / 1.28 ms: this entry is 2 x to 3 x SLOWER than torch for
+ * a sum formed once on that class (and on the 9.4 M stand-in: 1.5 / 1.2 / 0.97 ms against 0.56 / 0.42 / 0.42).  It pays for the census,
+ * for the map of the next entry and for two synchronising reads; how its time splits between the passes has not been separated. */
+int spmv_acc_csr_add(int m, int n,
+                     int nnz_a, const int *d_a_rowptr, const int *d_a_colindex,
+                     int nnz_b, const int *d_b_rowptr, const int *d_b_colindex,
+                     double alpha, const double *d_a_value, double beta, const double *d_b_value,
+                     int *d_c_rowptr, int *d_c_colindex, double *d_c_value,
+                     int *d_ia, int *d_ib, int *h_nnz);
+
+/* ---- sparse add C = alpha * A + beta * B, 2: new values, alpha or beta on a known pattern (new; the per-step hot path) ------------------
+ * replaces: nothing in the reference.  d_c_value[j] for j < nnz_c by the VALUES rule above, through the map (d_ia, d_ib) and nnz_c =
+ * *h_nnz of an earlier spmv_acc_csr_add on the same two patterns; nnz_a / nnz_b are the lengths of the value arrays.  The first entry
+ * runs this kernel for its own values, so the same values repeat its bits.  The map is the caller's array here: an index outside
+ * [0, nnz_a) / [0, nnz_b) -- this includes -1 -- counts as absent and is never turned into an address; an entry with both absent is
+ * +0.0.  d_c_value must NOT overlap d_a_value or d_b_value (entries are not read and written in the same order).
+ * One kernel on the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy; may be captured into a
+ * hipGraph.  alpha and beta are kernel arguments: a captured launch keeps the alpha and beta it was captured with, only the arrays'
+ * contents follow the caller (capture again, or update the graph node, for a new dt).  Negative sizes, or a null pointer where data is
+ * needed with nnz_c > 0: SPMV_ACC_ERR_BAD_ARGUMENT; a size beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE; nnz_c == 0: nothing.  Per C
+ * entry it streams 8 B of map, gathers 8 B per present operand (both maps ascend apart from the -1 gaps: near-sequential) and stores
+ * 8 B.  Returns 0 or an spmv_acc_error code.
+ * COST, as measured (same run): 0.90 to 0.92 of the box's copy rate on the bytes it needs, on every job of the two large stand-ins.
+ * Headline stand-in, M + dt K: 0.214 ms = 6.05 TB/s, 1.5 SpMVs (torch's whole add: 8.3 ms); A + sigma I 0.193 ms.  FEM class: A + A^T
+ * 0.170 ms, M + dt K 0.149 ms, A + sigma I 0.116 ms = 2.4 to 3.5 SpMVs, 8 x to 11 x faster than torch's whole add.  The 9.4 M stand-in
+ * reads 0.93 to 1.02 of the copy rate (0.037 to 0.051 ms; supposed, not checked: part of its arrays stays in the last-level cache). */
+int spmv_acc_csr_add_values(int nnz_c, int nnz_a, int nnz_b, const int *d_ia, const int *d_ib,
+                            double alpha, const double *d_a_value, double beta, const double *d_b_value,
+                            double *d_c_value);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

@@ -43,6 +43,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_spmm", "spmv_acc_csr_transpose", "spmv_acc_csr_transpose_values", "spmv_acc_csr_spmv_t",
     "spmv_acc_coo_to_csr", "spmv_acc_coo_to_csr_values",
     "spmv_acc_csr_spgemm_products", "spmv_acc_csr_spgemm", "spmv_acc_csr_spgemm_values",
+    "spmv_acc_csr_add", "spmv_acc_csr_add_values",
 )
 
 _lib = None
@@ -155,6 +156,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_spgemm.restype = ci
     lib.spmv_acc_csr_spgemm_values.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
     lib.spmv_acc_csr_spgemm_values.restype = ci
+    lib.spmv_acc_csr_add.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, ctypes.c_double, vp, ctypes.c_double, vp, vp, vp, vp, vp, vp, _c_int_p]
+    lib.spmv_acc_csr_add.restype = ci
+    lib.spmv_acc_csr_add_values.argtypes = [ci, ci, ci, vp, vp, ctypes.c_double, vp, ctypes.c_double, vp, vp]
+    lib.spmv_acc_csr_add_values.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -519,6 +524,75 @@ def csr_spgemm_values(pa, pb, start, a_value, b_value, out) -> None:
     if rc != 0:
         _check(lib)
         raise SpmvAccError(f"csr_spgemm_values failed ({rc})")
+
+
+def csr_add(m: int, n: int, a_rowptr, a_colindex, a_value, b_rowptr, b_colindex, b_value, alpha: float = 1.0, beta: float = 1.0,
+            want_map: bool = False):
+    """Device sparse add C = alpha * A + beta * B (spmv_acc_csr_add), A and B both m x n in rebased CSR with every row strictly ascending in
+    column (what coo_to_csr, csr_transpose and csr_spgemm return): returns new GPU tensors (rowptr, colindex, value | None[, ia, ib]).  Row i of
+    C is the sorted union of the two rows, nothing pruned; ia[j] / ib[j] = the position of entry j in A's / B's arrays or -1; value[j] =
+    alpha * a[ia[j]] + beta * b[ib[j]] with each product rounded and an absent side left out (not added as 0.0) -- unique, bit for bit.
+    a_value = b_value = None: structure only.  ia / ib: the map for csr_add_values.  len(a_colindex) / len(b_colindex) must be a_rowptr[m] /
+    b_rowptr[m].  This wrapper allocates arrays of the upper bound nnz_a + nnz_b and returns EXACT-size tensors by cloning the used prefixes.
+    Synchronises; not capturable."""
+    import torch
+
+    lib = load_library()
+    if m < 0 or n < 0:
+        raise SpmvAccError(f"negative shape ({m}, {n})")
+    _require_tensors(a_rowptr=a_rowptr, a_colindex=a_colindex, b_rowptr=b_rowptr, b_colindex=b_colindex)
+    nnz_a, nnz_b = int(a_colindex.numel()), int(b_colindex.numel())
+    named = dict(a_rowptr=(a_rowptr, "i32", m + 1), a_colindex=(a_colindex, "i32", 0), b_rowptr=(b_rowptr, "i32", m + 1),
+                 b_colindex=(b_colindex, "i32", 0))
+    if (a_value is None) != (b_value is None):
+        raise SpmvAccError("a_value and b_value must both be given or both be None (structure only)")
+    if a_value is not None:
+        _require_tensors(a_value=a_value, b_value=b_value)
+        if int(a_value.numel()) > nnz_a or int(b_value.numel()) > nnz_b:  # (fewer: the "elements" check below)
+            raise SpmvAccError(f"a_colindex / b_colindex hold {nnz_a} / {nnz_b} elements, a_value / b_value must hold as many")
+        named.update(a_value=(a_value, "f64", nnz_a), b_value=(b_value, "f64", nnz_b))
+    _require(lib, **named)
+    cap = nnz_a + nnz_b
+    dev = a_rowptr.device
+    rowptr = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    colindex = torch.empty(cap, dtype=torch.int32, device=dev)
+    value = None if a_value is None else torch.empty(cap, dtype=torch.float64, device=dev)
+    ia = torch.empty(cap, dtype=torch.int32, device=dev) if want_map else None
+    ib = torch.empty(cap, dtype=torch.int32, device=dev) if want_map else None
+    h_nnz = ctypes.c_int(0)
+    # (empty tensors have null pointers.  An index array without elements is not read; the value pointers form a group with c_value, so the
+    # one of a matrix without non-zeros -- never read either -- stands in as rowptr's, and with nothing to add the whole group stays null)
+    values = (0, 0, 0) if value is None or cap == 0 else tuple(_ptr(t) if t.numel() else _ptr(rowptr) for t in (a_value, b_value, value))
+    maps = tuple(_ptr(t) if t is not None and cap else 0 for t in (ia, ib))
+    rc = lib.spmv_acc_csr_add(m, n, nnz_a, _ptr(a_rowptr), _ptr(a_colindex) if nnz_a else 0, nnz_b, _ptr(b_rowptr), _ptr(b_colindex) if nnz_b else 0,
+                              alpha, values[0], beta, values[1], _ptr(rowptr), _ptr(colindex) if cap else 0, values[2], maps[0], maps[1],
+                              ctypes.byref(h_nnz))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_add failed ({rc})")
+    nnz = int(h_nnz.value)
+    out = (rowptr, colindex[:nnz].clone(), None if value is None else value[:nnz].clone())
+    return out + (ia[:nnz].clone(), ib[:nnz].clone()) if want_map else out
+
+
+def csr_add_values(ia, ib, a_value, b_value, out, alpha: float = 1.0, beta: float = 1.0) -> None:
+    """out[j] = alpha * a_value[ia[j]] + beta * b_value[ib[j]] by csr_add's rule (spmv_acc_csr_add_values, async on torch's current stream,
+    capturable): the values of C for new values of A and / or B, or a new alpha / beta, on known patterns, with the map csr_add(...,
+    want_map=True) returned; len(out) = len(ia) = len(ib) = nnz(C).  A map index outside the value array (-1 included) counts as absent; both
+    absent gives +0.0.  The same kernel as csr_add, so the same values give the same bits.  A captured launch keeps the alpha and beta it was
+    captured with.  out must not overlap a_value or b_value."""
+    lib = load_library()
+    _require_tensors(ia=ia, ib=ib, a_value=a_value, b_value=b_value, out=out)
+    nnz_c = int(ia.numel())
+    if int(ib.numel()) > nnz_c or int(out.numel()) > nnz_c:  # (fewer: the "elements" check below)
+        raise SpmvAccError(f"ia holds {nnz_c} elements, ib and out must hold as many")
+    _require(lib, ia=(ia, "i32", nnz_c), ib=(ib, "i32", nnz_c), a_value=(a_value, "f64", 0), b_value=(b_value, "f64", 0), out=(out, "f64", nnz_c))
+    nnz_a, nnz_b = int(a_value.numel()), int(b_value.numel())
+    rc = lib.spmv_acc_csr_add_values(nnz_c, nnz_a, nnz_b, _ptr(ia) if nnz_c else 0, _ptr(ib) if nnz_c else 0, alpha, _ptr(a_value) if nnz_a else 0,
+                                     beta, _ptr(b_value) if nnz_b else 0, _ptr(out) if nnz_c else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_add_values failed ({rc})")
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

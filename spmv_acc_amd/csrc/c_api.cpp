@@ -16,6 +16,7 @@
 #include "transpose.hpp"
 #include "coo.hpp"
 #include "spgemm.hpp"
+#include "csr_add.hpp"
 
 #include <string>
 #include <cstdint>
@@ -237,6 +238,18 @@ int spmv_acc_csr_spgemm(int m, int k, int n, int nnz_a, const int *d_a_rowptr, c
 int spmv_acc_csr_spgemm_values(int nprod, int nnz_c, const int *d_pa, const int *d_pb, const int *d_start, const double *d_a_value,
                                const double *d_b_value, double *d_c_value) {
   return run_csr_spgemm_values(nprod, nnz_c, d_pa, d_pb, d_start, d_a_value, d_b_value, d_c_value);
+}
+
+int spmv_acc_csr_add(int m, int n, int nnz_a, const int *d_a_rowptr, const int *d_a_colindex, int nnz_b, const int *d_b_rowptr,
+                     const int *d_b_colindex, double alpha, const double *d_a_value, double beta, const double *d_b_value, int *d_c_rowptr,
+                     int *d_c_colindex, double *d_c_value, int *d_ia, int *d_ib, int *h_nnz) {
+  return run_csr_add(m, n, nnz_a, d_a_rowptr, d_a_colindex, nnz_b, d_b_rowptr, d_b_colindex, alpha, d_a_value, beta, d_b_value, d_c_rowptr,
+                     d_c_colindex, d_c_value, d_ia, d_ib, h_nnz);
+}
+
+int spmv_acc_csr_add_values(int nnz_c, int nnz_a, int nnz_b, const int *d_ia, const int *d_ib, double alpha, const double *d_a_value, double beta,
+                            const double *d_b_value, double *d_c_value) {
+  return run_csr_add_values(nnz_c, nnz_a, nnz_b, d_ia, d_ib, alpha, d_a_value, beta, d_b_value, d_c_value);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
