@@ -363,6 +363,70 @@ int spmv_acc_csr_add_values(int nnz_c, int nnz_a, int nnz_b, const int *d_ia, co
                             double alpha, const double *d_a_value, double beta, const double *d_b_value,
                             double *d_c_value);
 
+/* ---- extraction C = A[rows, colmap] with a diagonal band, 1: structure, map and first values (new) ----------------------------------------
+ * replaces: nothing in the reference.  Takes a matrix apart or renumbers it on the device: the symmetric permutation P A P^T (rows = perm,
+ * colmap = its inverse), sub-blocks A[I, J] (Schur complements with spmv_acc_csr_spgemm and spmv_acc_csr_add, a local / halo column split),
+ * the triangles and the diagonal of A as CSR matrices (L + D + U), and a row-sorted copy of an unsorted CSR (what spmv_acc_csr_add demands).
+ * INPUTS: A is m x n, CSR, int32, fp64, rebased (rowptr[0] == 0); its rows may be in ANY column order and may repeat a column.  nnz_a must be
+ * rowptr[m], or negative: read from the device.  d_rows[mc]: row i of C is row rows[i] of A; the rows must be distinct; NULL: rows[i] = i, and
+ * then mc must equal m.  d_colmap[n]: an entry with column c gets the new column colmap[c]; a negative value drops the column, the non-negative
+ * values must be distinct and < nc; NULL: the identity, and then nc must equal n; nc may exceed n (embedding).  diag_lo, diag_hi: an entry at
+ * (i, j) of C is kept iff diag_lo <= (long long)j - i <= diag_hi, in C's OWN indices: INT_MIN, INT_MAX keeps everything; 0, 0 the diagonal;
+ * INT_MIN, 0 the lower triangle; 1, INT_MAX the strict upper; diag_lo > diag_hi is legal and gives an empty C.
+ * THE RESULT IS UNIQUE (no implementation choice can change a bit of it).  C is mc x nc.  Row i of C holds the kept entries of row rows[i] of
+ * A in ascending new column; entries of equal new column occur only where A's row repeats a column, and stay in ascending position of A.  C
+ * has strictly ascending rows exactly when the selected rows of A repeat no column.  MAP: d_map[j] = the position of C entry j in A's arrays.
+ * VALUES: c_value[j] = a_value[map[j]], the bits copied with no arithmetic (-0.0 and NaN payloads survive); nothing is pruned by value.
+ * *h_nnz (a host int) = nnz(C) <= nnz_a.  Rows of A that are not selected are never read, and so never checked.
+ * OUTPUTS, all owned by the caller: d_c_rowptr (mc + 1 ints); d_c_colindex, d_c_value, d_map sized nnz_a (the upper bound, no count entry is
+ * needed); only their first *h_nnz elements are written.  d_a_value and d_c_value both NULL: structure only; exactly one of them NULL is
+ * SPMV_ACC_ERR_BAD_ARGUMENT.  d_map may be NULL (with values, a copy lives in the workspace and is dropped).  d_c_value must not overlap
+ * d_a_value, and no output may overlap an input.
+ * CHECKS.  On the host, before the device is touched: negative m, n, mc or nc, null pointers where data is needed, d_rows == NULL with mc != m,
+ * d_colmap == NULL with nc != n: SPMV_ACC_ERR_BAD_ARGUMENT; m, n, mc, nc or nnz_a beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE -- rows of C
+ * are independent, so extract row ranges.  On the device, each SPMV_ACC_ERR_BAD_ARGUMENT: rowptr[0] != 0; a given nnz_a that is not rowptr[m];
+ * and ONE CENSUS before anything reads through an index, counting (a) rows outside [0, m), (b) repeated rows, (c) selected rows whose rowptr
+ * extent descends or leaves [0, nnz_a], (d) colmap values >= nc, (e) repeated non-negative colmap values, then (f) candidates -- entries of
+ * the selected rows -- whose column lies outside [0, n): if any count is non-zero nothing was written and the error string holds the counts.
+ * mc == 0, m == 0, nnz_a == 0 or no candidate: d_c_rowptr all zeros, *h_nnz = 0, nothing else is touched (so too when nothing is kept).
+ * Runs on the calling thread's library stream and has finished when it returns.  A stable compaction of the candidates, then a count of the
+ * descents inside the rows of the result: with none (sorted rows under an identity or order-preserving colmap: sub-blocks, triangles, row
+ * gathers) that is the answer; otherwise one stable radix sort by (row, new column).  Both give the same bits.  All passes are cut by
+ * candidates or C entries, none by rows, and there is no atomic: two calls on the same inputs give the same bits, tunable "deterministic"
+ * changes nothing.  WORKSPACE, three allocations, freed on every path: 4 B per row of A (with d_rows), 4 B per column of C (with d_colmap),
+ * 8 B per row of C, 112 KiB of census counts; per candidate 8 B, 12 B when values are wanted without a map; only when a sort is needed, per
+ * entry of C 20 B without and 24 B with a map, and the radix sort's scratch (about 12 B per entry).  Inside a stream capture it enqueues
+ * nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan.  Returns 0 or an spmv_acc_error code (also left in
+ * spmv_acc_last_error).
+ * COST, as measured (MI355X, tools/extract_bench.py, profiles/extract_bench.md; the box copied at 6.63 TB/s in the same run; stand-ins made
+ * canonical by spmv_acc_coo_to_csr first; beside each the plain torch composition a user would write today: expand the rows, map, mask, one
+ * stable sort of the keys, bincount -- its result equals this entry's bit for bit in every job).  Headline stand-in (40.5 M entries, settled
+ * SpMV 0.146 ms): random row and column permutations (sort path) 12.5 ms = 85 SpMVs, torch 11.7 ms -- torch is 6 % FASTER there; the strict
+ * lower triangle (no sort) 6.8 ms against 10.6 ms; a contiguous half-by-half block 3.7 ms against 5.7 ms.  FEM class (28.2 M entries, SpMV
+ * 0.051 ms): a random symmetric permutation 6.5 ms = 128 SpMVs against 7.6 ms; strict lower 3.0 ms against 4.8 ms; block 2.1 ms against
+ * 4.0 ms.  How the time splits between the census, the two scans, the sort and the four synchronising reads has not been separated. */
+int spmv_acc_csr_extract(int m, int n, int nnz_a, const int *d_a_rowptr, const int *d_a_colindex, const double *d_a_value,
+                         int mc, const int *d_rows, int nc, const int *d_colmap, int diag_lo, int diag_hi,
+                         int *d_c_rowptr, int *d_c_colindex, double *d_c_value, int *d_map, int *h_nnz);
+
+/* ---- extraction C = A[rows, colmap] with a diagonal band, 2: new values on a known pattern (new; the per-step hot path) --------------------
+ * replaces: nothing in the reference.  d_c_value[j] = d_a_value[d_map[j]] for j < nnz_c, through the map and nnz_c = *h_nnz of an earlier
+ * spmv_acc_csr_extract on the same pattern; nnz_a is the length of d_a_value.  The first entry runs this kernel for its own values, so the
+ * same values repeat its bits.  The map is the caller's array here: an index outside [0, nnz_a) -- this includes -1 -- gives +0.0 and is
+ * never turned into an address.  d_c_value must NOT overlap d_a_value (entries are not read and written in the same order).
+ * (spmv_acc_csr_transpose_values cannot serve: it bounds its map by the one nnz it is given, and here nnz(C) != nnz(A).)
+ * One kernel on the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy; may be captured into a
+ * hipGraph.  Negative sizes, or a null pointer where data is needed with nnz_c > 0: SPMV_ACC_ERR_BAD_ARGUMENT; a size beyond INT_MAX - 2^16:
+ * SPMV_ACC_ERR_TOO_LARGE; nnz_c == 0: nothing.  Per C entry it streams 4 B of map, gathers 8 B and stores 8 B: 20 B.  Returns 0 or an
+ * spmv_acc_error code.
+ * COST, as measured (same run; rates on the 20 B an entry needs, relative to the box's copy rate).  Headline stand-in: the monotone map of
+ * the strict lower triangle, 38.6 M entries, 0.133 ms = 0.88 of the copy rate, 0.9 SpMVs; the map of random row and column permutations
+ * 0.266 ms = 0.46 (every missed gather is a whole memory request).  FEM class: a random symmetric permutation, whose rows of 30 entries stay
+ * contiguous runs of the map, 0.102 ms = 0.84; the strict lower triangle, 13.9 M entries out of every other run of A's values, 0.068 ms =
+ * 0.62 (the lines it gathers from are half used; supposed, not checked).  torch.index_select(a_value, 0, map) into a preallocated tensor takes
+ * 0.263 / 0.142 / 0.112 / 0.072 ms on the same four maps: within 1 % on the permuted headline map (torch ahead), 6 to 9 % slower elsewhere. */
+int spmv_acc_csr_extract_values(int nnz_c, int nnz_a, const int *d_map, const double *d_a_value, double *d_c_value);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

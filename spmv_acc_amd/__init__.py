@@ -44,6 +44,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_coo_to_csr", "spmv_acc_coo_to_csr_values",
     "spmv_acc_csr_spgemm_products", "spmv_acc_csr_spgemm", "spmv_acc_csr_spgemm_values",
     "spmv_acc_csr_add", "spmv_acc_csr_add_values",
+    "spmv_acc_csr_extract", "spmv_acc_csr_extract_values",
 )
 
 _lib = None
@@ -160,6 +161,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_add.restype = ci
     lib.spmv_acc_csr_add_values.argtypes = [ci, ci, ci, vp, vp, ctypes.c_double, vp, ctypes.c_double, vp, vp]
     lib.spmv_acc_csr_add_values.restype = ci
+    lib.spmv_acc_csr_extract.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, _c_int_p]
+    lib.spmv_acc_csr_extract.restype = ci
+    lib.spmv_acc_csr_extract_values.argtypes = [ci, ci, vp, vp, vp]
+    lib.spmv_acc_csr_extract_values.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -593,6 +598,113 @@ def csr_add_values(ia, ib, a_value, b_value, out, alpha: float = 1.0, beta: floa
     if rc != 0:
         _check(lib)
         raise SpmvAccError(f"csr_add_values failed ({rc})")
+
+
+_INT_MIN, _INT_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def csr_extract(m: int, n: int, rowptr, colindex, value, rows=None, colmap=None, nc=None, diag_lo=None, diag_hi=None, want_map: bool = False):
+    """Device extraction C = A[rows, colmap] with a diagonal band (spmv_acc_csr_extract), A m x n in rebased CSR whose rows may be in any column
+    order and may repeat a column: returns new GPU tensors (rowptr, colindex, value | None[, map]).  Row i of C is row rows[i] of A (distinct
+    rows; None: every row, in order); a column c becomes colmap[c], a negative colmap[c] drops it, the others are distinct and < nc (None: the
+    identity, nc = n; nc defaults to n); an entry at (i, j) of C is kept iff diag_lo <= j - i <= diag_hi (None: unbounded on that side; 0, 0 the
+    diagonal; None, 0 the lower triangle; 1, None the strict upper).  Every row of C ascends in new column, equal columns (only where A's row
+    repeats one) in A's order; value[j] = a_value[map[j]], the bits copied -- unique, bit for bit.  value = None: structure only.  map: for
+    csr_extract_values.  len(colindex) must be rowptr[m].  This wrapper allocates arrays of the upper bound len(colindex) and returns
+    EXACT-size tensors by cloning the used prefixes.  Synchronises; not capturable."""
+    import torch
+
+    lib = load_library()
+    if m < 0 or n < 0:
+        raise SpmvAccError(f"negative shape ({m}, {n})")
+    _require_tensors(rowptr=rowptr, colindex=colindex)
+    nnz_a = int(colindex.numel())
+    named = dict(rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0))
+    if value is not None:
+        _require_tensors(value=value)
+        if int(value.numel()) > nnz_a:  # (fewer: the "elements" check below)
+            raise SpmvAccError(f"colindex holds {nnz_a} elements, value must hold as many")
+        named["value"] = (value, "f64", nnz_a)
+    mc = m
+    if rows is not None:
+        _require_tensors(rows=rows)
+        mc = int(rows.numel())
+        named["rows"] = (rows, "i32", 0)
+    if colmap is not None:
+        _require_tensors(colmap=colmap)
+        if int(colmap.numel()) > n:  # (fewer: the "elements" check below)
+            raise SpmvAccError(f"colmap holds {int(colmap.numel())} elements, A has {n} columns: it must hold as many")
+        named["colmap"] = (colmap, "i32", n)
+    nc = n if nc is None else int(nc)
+    if nc < 0:
+        raise SpmvAccError(f"negative nc ({nc})")
+    if colmap is None and nc != n:
+        raise SpmvAccError(f"colmap=None is the identity: nc ({nc}) must be n ({n})")
+    lo = _INT_MIN if diag_lo is None else int(diag_lo)
+    hi = _INT_MAX if diag_hi is None else int(diag_hi)
+    if not (_INT_MIN <= lo <= _INT_MAX and _INT_MIN <= hi <= _INT_MAX):
+        raise SpmvAccError(f"diag_lo / diag_hi ({lo}, {hi}) outside int32")
+    _require(lib, **named)
+    dev = rowptr.device
+    c_rowptr = torch.empty(mc + 1, dtype=torch.int32, device=dev)
+    c_colindex = torch.empty(nnz_a, dtype=torch.int32, device=dev)
+    c_value = None if value is None else torch.empty(nnz_a, dtype=torch.float64, device=dev)
+    cmap = torch.empty(nnz_a, dtype=torch.int32, device=dev) if want_map else None
+    h_nnz = ctypes.c_int(0)
+    # (empty tensors have null pointers.  An array without elements is not read; the two value pointers form a group, so with no non-zeros
+    # both stay null)
+    values = (0, 0) if value is None or nnz_a == 0 else (_ptr(value), _ptr(c_value))
+    rc = lib.spmv_acc_csr_extract(m, n, nnz_a, _ptr(rowptr), _ptr(colindex) if nnz_a else 0, values[0], mc,
+                                  _ptr(rows) if rows is not None and mc else (0 if rows is None else _ptr(c_rowptr)), nc,
+                                  _ptr(colmap) if colmap is not None and n else (0 if colmap is None else _ptr(c_rowptr)), lo, hi, _ptr(c_rowptr),
+                                  _ptr(c_colindex) if nnz_a else 0, values[1], _ptr(cmap) if want_map and nnz_a else 0, ctypes.byref(h_nnz))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_extract failed ({rc})")
+    nnz = int(h_nnz.value)
+    out = (c_rowptr, c_colindex[:nnz].clone(), None if c_value is None else c_value[:nnz].clone())
+    return out + (cmap[:nnz].clone(),) if want_map else out
+
+
+def csr_extract_values(map, a_value, out) -> None:
+    """out[j] = a_value[map[j]] (spmv_acc_csr_extract_values, async on torch's current stream, capturable): the values of C for new values of
+    A on a known pattern, with the map csr_extract(..., want_map=True) or csr_permute(..., want_map=True) returned; len(out) = len(map) =
+    nnz(C).  A map index outside the value array (-1 included) gives +0.0.  The same kernel as csr_extract, so the same values give the same
+    bits.  out must not overlap a_value."""
+    lib = load_library()
+    _require_tensors(map=map, a_value=a_value, out=out)
+    nnz_c = int(map.numel())
+    if int(out.numel()) > nnz_c:  # (fewer: the "elements" check below)
+        raise SpmvAccError(f"map holds {nnz_c} elements, out must hold as many")
+    _require(lib, map=(map, "i32", nnz_c), a_value=(a_value, "f64", 0), out=(out, "f64", nnz_c))
+    nnz_a = int(a_value.numel())
+    rc = lib.spmv_acc_csr_extract_values(nnz_c, nnz_a, _ptr(map) if nnz_c else 0, _ptr(a_value) if nnz_a else 0, _ptr(out) if nnz_c else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_extract_values failed ({rc})")
+
+
+def csr_permute(m: int, rowptr, colindex, value, perm, want_map: bool = False):
+    """The symmetric permutation C = P A P^T of a square m x m CSR: C[i, j] = A[perm[i], perm[j]] (csr_extract with rows = perm and colmap =
+    the inverse of perm, built on the device).  perm: m int32 entries on the GPU, a permutation of [0, m).  Its length and range are checked
+    here, with a reduction, before it is used as an index; a repeated entry leaves a hole in the inverse and is refused by the C entry's
+    distinct-rows check.  Returns what csr_extract returns."""
+    import torch
+
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(perm=perm)
+    if int(perm.numel()) != m:
+        raise SpmvAccError(f"perm holds {int(perm.numel())} elements, a permutation of the {m} rows must hold as many")
+    _require(lib, perm=(perm, "i32", m))
+    inverse = torch.full((m,), -1, dtype=torch.int32, device=perm.device)
+    if m:
+        low, high = int(perm.min()), int(perm.max())
+        if low < 0 or high >= m:
+            raise SpmvAccError(f"perm: values in [{low}, {high}], a permutation of the rows holds [0, {m})")
+        inverse[perm.long()] = torch.arange(m, dtype=torch.int32, device=perm.device)
+    return csr_extract(m, m, rowptr, colindex, value, rows=perm, colmap=inverse, nc=m, want_map=want_map)
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

@@ -17,6 +17,7 @@
 #include "coo.hpp"
 #include "spgemm.hpp"
 #include "csr_add.hpp"
+#include "extract.hpp"
 
 #include <string>
 #include <cstdint>
@@ -250,6 +251,17 @@ int spmv_acc_csr_add(int m, int n, int nnz_a, const int *d_a_rowptr, const int *
 int spmv_acc_csr_add_values(int nnz_c, int nnz_a, int nnz_b, const int *d_ia, const int *d_ib, double alpha, const double *d_a_value, double beta,
                             const double *d_b_value, double *d_c_value) {
   return run_csr_add_values(nnz_c, nnz_a, nnz_b, d_ia, d_ib, alpha, d_a_value, beta, d_b_value, d_c_value);
+}
+
+int spmv_acc_csr_extract(int m, int n, int nnz_a, const int *d_a_rowptr, const int *d_a_colindex, const double *d_a_value, int mc, const int *d_rows,
+                         int nc, const int *d_colmap, int diag_lo, int diag_hi, int *d_c_rowptr, int *d_c_colindex, double *d_c_value, int *d_map,
+                         int *h_nnz) {
+  return run_csr_extract(m, n, nnz_a, d_a_rowptr, d_a_colindex, d_a_value, mc, d_rows, nc, d_colmap, diag_lo, diag_hi, d_c_rowptr, d_c_colindex,
+                         d_c_value, d_map, h_nnz);
+}
+
+int spmv_acc_csr_extract_values(int nnz_c, int nnz_a, const int *d_map, const double *d_a_value, double *d_c_value) {
+  return run_csr_extract_values(nnz_c, nnz_a, d_map, d_a_value, d_c_value);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
