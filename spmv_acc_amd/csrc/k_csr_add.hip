@@ -20,8 +20,7 @@
 //    rounded on its own and the sum is one addition (fp contraction is off: a fused multiply-add would round once where the definition rounds twice);
 //    an absent side is left out by a select, never added as 0.0 (which would turn -0.0 into +0.0).
 #include "csr_add.hpp"
-#include "device_utils.hpp"
-#include "kernels.hpp"
+#include "structure_passes.hpp"
 
 #include <algorithm>
 
@@ -32,49 +31,7 @@ namespace spmv_acc {
 namespace {
 
 using namespace dev;
-
-unsigned csr_add_grid(long long items, int per_block) {
-  long long b = (items + per_block - 1) / per_block;
-  const long long cap = max_grid_blocks();
-  return static_cast<unsigned>(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-// row i as positions [lo, *hi) inside the matrix' arrays, whatever rowptr holds (0 <= i < m)
-__device__ __forceinline__ int csr_add_row(const int *__restrict__ rowptr, int nnz, int i, int *hi) {
-  int lo = rowptr[i], h = rowptr[i + 1];
-  lo = lo < 0 ? 0 : (lo > nnz ? nnz : lo);
-  *hi = h < lo ? lo : (h > nnz ? nnz : h);
-  return lo;
-}
-
-// the last row r in [lo, hi] with rowptr[r] <= q (lo itself if there is none): with an ascending rowptr and rowptr[lo] <= q < rowptr[hi + 1] the row
-// that holds non-zero q (empty rows are passed over).  Reads rowptr[lo + 1 .. hi] only
-__device__ __forceinline__ int csr_add_row_of(const int *__restrict__ rowptr, int lo, int hi, long long q) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (rowptr[mid] <= q) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// the first position p in [lo, hi) with col[p] >= c (hi if there is none)
-__device__ __forceinline__ int csr_add_lower_bound(const int *__restrict__ col, int lo, int hi, int c) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (col[mid] < c) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// the row of non-zero q for a wavefront that owns the consecutive non-zeros [first, last]: every lane the same two searches in rowptr[0 .. m) for the
-// rows of the ends, then its own between them
-__device__ __forceinline__ int csr_add_wave_row(const int *__restrict__ rowptr, int m, long long first, long long last, long long q) {
-  const int r_first = csr_add_row_of(rowptr, 0, m - 1, first);
-  const int r_last = csr_add_row_of(rowptr, r_first, m - 1, last);
-  return csr_add_row_of(rowptr, r_first, r_last, q);
-}
+using namespace passes;
 
 // gridDim.x <= kCooCheckBlocks; slots: csr_add.hpp launch_csr_add_census.  m > 0.
 __global__ __launch_bounds__(kThreads) void csr_add_census_kernel(int m, int n, int nnz_a, const int *__restrict__ a_rowptr,
@@ -94,9 +51,9 @@ __global__ __launch_bounds__(kThreads) void csr_add_census_kernel(int m, int n, 
     const long long last = (base + kWave < nnz ? base + kWave : nnz) - 1;
     const long long q = base + lane;
     if (q > last) continue;
-    const int i = csr_add_wave_row(rowptr, m, base, last, q); // (inside [0, m) whatever rowptr holds; a rowptr that does not ascend is counted below)
+    const int i = wave_row_of(rowptr, m, base, last, q); // (inside [0, m) whatever rowptr holds; a rowptr that does not ascend is counted below)
     int hi;
-    const int lo = csr_add_row(rowptr, nnz, i, &hi);
+    const int lo = row_extent(rowptr, nnz, i, &hi);
     const int c = col[q];
     out_of_range += static_cast<unsigned>(c) >= static_cast<unsigned>(n) ? 1u : 0u;
     not_ascending += q > lo && c <= col[q - 1] ? 1u : 0u;
@@ -106,17 +63,10 @@ __global__ __launch_bounds__(kThreads) void csr_add_census_kernel(int m, int n, 
     const int lo = rowptr[r], hi = rowptr[r + 1];
     bad_rows += lo < 0 || hi > nnz || hi < lo ? 1u : 0u;
   }
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    out_of_range += __shfl_xor(out_of_range, off, kWave);
-    not_ascending += __shfl_xor(not_ascending, off, kWave);
-    bad_rows += __shfl_xor(bad_rows, off, kWave);
-  }
-  if (lane == 0) { // (blockIdx.x < kCooCheckBlocks: a slot of its own per wavefront and count)
-    unsigned *mine = slots + (second ? 3 * kCooCheckSlots : 0) + blockIdx.x * (kThreads / kWave) + wave;
-    mine[0] = out_of_range;
-    mine[kCooCheckSlots] = not_ascending;
-    mine[2 * kCooCheckSlots] = bad_rows;
-  }
+  unsigned *mine = slots + (second ? 3 * kCooCheckSlots : 0); // (a slot of its own per wavefront and count)
+  count_to_slot(out_of_range, mine);
+  count_to_slot(not_ascending, mine + kCooCheckSlots);
+  count_to_slot(bad_rows, mine + 2 * kCooCheckSlots);
 }
 
 // One workgroup per tile of kCsrAddRankTile of the nnz_a + 1 items, blocks stride over the tiles beyond the grid.  m > 0.
@@ -137,11 +87,11 @@ __global__ __launch_bounds__(kThreads) void csr_add_match_kernel(int m, int nnz_
       bpos[q] = -1; // (the scan's closing element: no match)
       continue;
     }
-    const int i = csr_add_wave_row(a_rowptr, m, base, last, q);
+    const int i = wave_row_of(a_rowptr, m, base, last, q);
     int hi;
-    const int lo = csr_add_row(b_rowptr, nnz_b, i, &hi);
+    const int lo = row_extent(b_rowptr, nnz_b, i, &hi);
     const int c = a_colindex[q];
-    const int pos = csr_add_lower_bound(b_colindex, lo, hi, c);
+    const int pos = first_at_least(b_colindex, lo, hi, c);
     bpos[q] = pos < hi && b_colindex[pos] == c ? pos : ~pos;
   }
 }
@@ -190,11 +140,11 @@ __global__ __launch_bounds__(kThreads) void csr_add_place_b_kernel(int m, int nn
     const long long last = (base + kWave < nnz_b ? base + kWave : nnz_b) - 1;
     const long long t = base + lane;
     if (t > last) continue;
-    const int i = csr_add_wave_row(b_rowptr, m, base, last, t);
+    const int i = wave_row_of(b_rowptr, m, base, last, t);
     int hi;
-    const int lo = csr_add_row(a_rowptr, nnz_a, i, &hi);
+    const int lo = row_extent(a_rowptr, nnz_a, i, &hi);
     const int c = b_colindex[t];
-    const int apos = csr_add_lower_bound(a_colindex, lo, hi, c); // (0 <= apos <= nnz_a: ms holds nnz_a + 1 elements)
+    const int apos = first_at_least(a_colindex, lo, hi, c); // (0 <= apos <= nnz_a: ms holds nnz_a + 1 elements)
     if (apos < hi && a_colindex[apos] == c) continue;            // A holds the column: its lane wrote the entry
     int j = static_cast<int>(t) + apos - ms[apos];
     j = j < 0 ? 0 : (j >= cap ? cap - 1 : j);
@@ -258,16 +208,14 @@ void launch_csr_add_census(hipStream_t stream, int m, int n, int nnz_a, const in
                            const int *b_colindex, unsigned *slots) {
   if (m <= 0) return;
   const long long items = std::max(static_cast<long long>(std::max(nnz_a, nnz_b)), static_cast<long long>(m));
-  unsigned grid = csr_add_grid(items, kCsrAddRankTile);
-  grid = grid > static_cast<unsigned>(kCooCheckBlocks) ? static_cast<unsigned>(kCooCheckBlocks) : grid;
-  SPMV_ACC_LAUNCH(csr_add_census_kernel, dim3(grid, 2), dim3(kThreads), 0, stream, m, n, nnz_a, a_rowptr, a_colindex, nnz_b, b_rowptr, b_colindex,
-                  slots);
+  SPMV_ACC_LAUNCH(csr_add_census_kernel, dim3(census_grid_for(items, kCsrAddRankTile), 2), dim3(kThreads), 0, stream, m, n, nnz_a, a_rowptr, a_colindex,
+                  nnz_b, b_rowptr, b_colindex, slots);
 }
 
 void launch_csr_add_match(hipStream_t stream, int m, int nnz_a, const int *a_rowptr, const int *a_colindex, int nnz_b, const int *b_rowptr,
                           const int *b_colindex, int *bpos) {
   if (m <= 0) return;
-  SPMV_ACC_LAUNCH(csr_add_match_kernel, dim3(csr_add_grid(static_cast<long long>(nnz_a) + 1, kCsrAddRankTile)), dim3(kThreads), 0, stream, m, nnz_a,
+  SPMV_ACC_LAUNCH(csr_add_match_kernel, dim3(grid_for(static_cast<long long>(nnz_a) + 1, kCsrAddRankTile)), dim3(kThreads), 0, stream, m, nnz_a,
                   a_rowptr, a_colindex, nnz_b, b_rowptr, b_colindex, bpos);
 }
 
@@ -278,28 +226,28 @@ bool launch_csr_add_scan(hipStream_t stream, const int *bpos, int nnz_a, int *ms
 
 void launch_csr_add_rowptr(hipStream_t stream, int m, int nnz_a, const int *a_rowptr, const int *b_rowptr, const int *ms, int *c_rowptr) {
   if (m <= 0) return;
-  SPMV_ACC_LAUNCH(csr_add_rowptr_kernel, dim3(csr_add_grid(static_cast<long long>(m) + 1, kThreads)), dim3(kThreads), 0, stream, m, nnz_a, a_rowptr,
+  SPMV_ACC_LAUNCH(csr_add_rowptr_kernel, dim3(grid_for(static_cast<long long>(m) + 1, kThreads)), dim3(kThreads), 0, stream, m, nnz_a, a_rowptr,
                   b_rowptr, ms, c_rowptr);
 }
 
 void launch_csr_add_place_a(hipStream_t stream, int nnz_a, int nnz_b, const int *a_colindex, const int *bpos, const int *ms, int *c_colindex, int *ia,
                             int *ib) {
   if (nnz_a <= 0) return;
-  SPMV_ACC_LAUNCH(csr_add_place_a_kernel, dim3(csr_add_grid(nnz_a, kCsrAddRankTile)), dim3(kThreads), 0, stream, nnz_a, nnz_a + nnz_b, a_colindex, bpos,
+  SPMV_ACC_LAUNCH(csr_add_place_a_kernel, dim3(grid_for(nnz_a, kCsrAddRankTile)), dim3(kThreads), 0, stream, nnz_a, nnz_a + nnz_b, a_colindex, bpos,
                   ms, c_colindex, ia, ib);
 }
 
 void launch_csr_add_place_b(hipStream_t stream, int m, int nnz_a, const int *a_rowptr, const int *a_colindex, int nnz_b, const int *b_rowptr,
                             const int *b_colindex, const int *ms, int *c_colindex, int *ia, int *ib) {
   if (m <= 0 || nnz_b <= 0) return;
-  SPMV_ACC_LAUNCH(csr_add_place_b_kernel, dim3(csr_add_grid(nnz_b, kCsrAddRankTile)), dim3(kThreads), 0, stream, m, nnz_a, a_rowptr, a_colindex, nnz_b,
+  SPMV_ACC_LAUNCH(csr_add_place_b_kernel, dim3(grid_for(nnz_b, kCsrAddRankTile)), dim3(kThreads), 0, stream, m, nnz_a, a_rowptr, a_colindex, nnz_b,
                   nnz_a + nnz_b, b_rowptr, b_colindex, ms, c_colindex, ia, ib);
 }
 
 void launch_csr_add_values(hipStream_t stream, int nnz_c, int nnz_a, int nnz_b, const int *ia, const int *ib, double alpha, const double *a_value,
                            double beta, const double *b_value, double *value) {
   if (nnz_c <= 0) return;
-  SPMV_ACC_LAUNCH(csr_add_values_kernel, dim3(csr_add_grid(nnz_c, kCsrAddTile)), dim3(kThreads), 0, stream, nnz_c, nnz_a, nnz_b, ia, ib, alpha, a_value,
+  SPMV_ACC_LAUNCH(csr_add_values_kernel, dim3(grid_for(nnz_c, kCsrAddTile)), dim3(kThreads), 0, stream, nnz_c, nnz_a, nnz_b, ia, ib, alpha, a_value,
                   beta, b_value, value);
 }
 

@@ -20,8 +20,7 @@
 //    and stores 8 B.  Lane l of a wavefront owns the kExtractPerLane entries base + l + 64 k: all map loads are issued, then all gathers, then
 //    the stores.  The bits are copied: no arithmetic touches a value.
 #include "extract.hpp"
-#include "device_utils.hpp"
-#include "kernels.hpp"
+#include "structure_passes.hpp"
 
 #include <algorithm>
 
@@ -32,52 +31,8 @@ namespace spmv_acc {
 namespace {
 
 using namespace dev;
+using namespace passes;
 using u64 = unsigned long long;
-
-unsigned extract_grid(long long items, int per_block) {
-  long long b = (items + per_block - 1) / per_block;
-  const long long cap = max_grid_blocks();
-  return static_cast<unsigned>(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-// a grid whose wavefronts each own a count slot
-unsigned extract_census_grid(long long items, int per_block) {
-  const unsigned grid = extract_grid(items, per_block);
-  return grid > static_cast<unsigned>(kCooCheckBlocks) ? static_cast<unsigned>(kCooCheckBlocks) : grid;
-}
-
-// row r of A as positions [lo, *hi) inside its arrays, whatever a_rowptr holds (0 <= r < m)
-__device__ __forceinline__ int extract_row(const int *__restrict__ rowptr, int nnz, int r, int *hi) {
-  int lo = rowptr[r], h = rowptr[r + 1];
-  lo = lo < 0 ? 0 : (lo > nnz ? nnz : lo);
-  *hi = h < lo ? lo : (h > nnz ? nnz : h);
-  return lo;
-}
-
-// the last row r in [lo, hi] with ptr[r] <= q (lo itself if there is none): with an ascending ptr and ptr[lo] <= q < ptr[hi + 1] the row that
-// holds item q (empty rows are passed over).  Reads ptr[lo + 1 .. hi] only
-__device__ __forceinline__ int extract_row_of(const int *__restrict__ ptr, int lo, int hi, long long q) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (ptr[mid] <= q) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// the row of item q for a wavefront that owns the consecutive items [first, last]: every lane the same two searches in ptr[0 .. rows) for the
-// rows of the ends, then its own between them
-__device__ __forceinline__ int extract_wave_row(const int *__restrict__ ptr, int rows, long long first, long long last, long long q) {
-  const int r_first = extract_row_of(ptr, 0, rows - 1, first);
-  const int r_last = extract_row_of(ptr, r_first, rows - 1, last);
-  return extract_row_of(ptr, r_first, r_last, q);
-}
-
-// the per-wavefront count of a census kernel into its slot (blockIdx.x < kCooCheckBlocks); every lane of the wavefront calls it
-__device__ __forceinline__ void extract_count(unsigned count, unsigned *__restrict__ group) {
-  for (int off = kWave / 2; off > 0; off >>= 1) count += __shfl_xor(count, off, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0) group[blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave] = count;
-}
 
 __global__ __launch_bounds__(kThreads) void extract_mark_kernel(int mc, int m, const int *__restrict__ rows, int *__restrict__ inv_row, int n, int nc,
                                                                 const int *__restrict__ colmap, int *__restrict__ inv_col) {
@@ -114,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void extract_census_kernel(int mc, int m,
         const int lo = a_rowptr[r], hi = a_rowptr[r + 1];
         bad_extents += lo < 0 || hi > nnz_a || hi < lo ? 1u : 0u;
         int h;
-        const int l = extract_row(a_rowptr, nnz_a, r, &h);
+        const int l = row_extent(a_rowptr, nnz_a, r, &h);
         length = h - l;
       }
     }
@@ -126,11 +81,11 @@ __global__ __launch_bounds__(kThreads) void extract_census_kernel(int mc, int m,
       if (v >= nc) map_out += 1u;
       else if (v >= 0) map_again += inv_col[v] != c ? 1u : 0u;
     }
-  extract_count(rows_out, slots);
-  extract_count(rows_again, slots + kCooCheckSlots);
-  extract_count(bad_extents, slots + 2 * kCooCheckSlots);
-  extract_count(map_out, slots + 3 * kCooCheckSlots);
-  extract_count(map_again, slots + 4 * kCooCheckSlots);
+  count_to_slot(rows_out, slots);
+  count_to_slot(rows_again, slots + kCooCheckSlots);
+  count_to_slot(bad_extents, slots + 2 * kCooCheckSlots);
+  count_to_slot(map_out, slots + 3 * kCooCheckSlots);
+  count_to_slot(map_again, slots + 4 * kCooCheckSlots);
 }
 
 // One workgroup per tile of kExtractRankTile of the S + 1 items, blocks stride over the tiles beyond the grid; gridDim.x <= kCooCheckBlocks.
@@ -155,9 +110,9 @@ __global__ __launch_bounds__(kThreads) void extract_candidates_kernel(int mc, in
       newcol[s] = -1; // (the scan's closing element: not kept)
       continue;
     }
-    const int i = extract_wave_row(src_ptr, mc, base, last < S ? last : S - 1, s);
+    const int i = wave_row_of(src_ptr, mc, base, last < S ? last : S - 1, s);
     int hi;
-    const int lo = extract_row(a_rowptr, nnz_a, rows != nullptr ? rows[i] : i, &hi);
+    const int lo = row_extent(a_rowptr, nnz_a, rows != nullptr ? rows[i] : i, &hi);
     long long q = lo + (s - src_ptr[i]); // (lo <= q < hi by the census; held inside A's arrays regardless)
     q = q < 0 ? 0 : (q >= nnz_a ? nnz_a - 1 : q);
     const int c = load_stream(a_colindex + q);
@@ -171,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void extract_candidates_kernel(int mc, in
     }
     newcol[s] = kept;
   }
-  extract_count(out_of_range, slots);
+  count_to_slot(out_of_range, slots);
 }
 
 __global__ __launch_bounds__(kThreads) void extract_rowptr_kernel(int mc, const int *__restrict__ src_ptr, const int *__restrict__ pos,
@@ -200,9 +155,9 @@ __global__ __launch_bounds__(kThreads) void extract_scatter_kernel(int mc, int n
     j = j < 0 ? 0 : (j >= cap ? cap - 1 : j);
     c_colindex[j] = col;
     if (map != nullptr) {
-      const int i = extract_wave_row(src_ptr, mc, base, last, s);
+      const int i = wave_row_of(src_ptr, mc, base, last, s);
       int hi;
-      const int lo = extract_row(a_rowptr, nnz_a, rows != nullptr ? rows[i] : i, &hi);
+      const int lo = row_extent(a_rowptr, nnz_a, rows != nullptr ? rows[i] : i, &hi);
       long long q = lo + (s - src_ptr[i]);
       q = q < 0 ? 0 : (q >= nnz_a ? nnz_a - 1 : q);
       map[j] = static_cast<int>(q);
@@ -223,10 +178,10 @@ __global__ __launch_bounds__(kThreads) void extract_descents_kernel(int mc, int 
     const long long last = (base + kWave < nnz_c ? base + kWave : nnz_c) - 1;
     const long long j = base + lane;
     if (j > last) continue;
-    const int i = extract_wave_row(c_rowptr, mc, base, last, j);
+    const int i = wave_row_of(c_rowptr, mc, base, last, j);
     descents += j > c_rowptr[i] && c_colindex[j] < c_colindex[j - 1] ? 1u : 0u;
   }
-  extract_count(descents, slots);
+  count_to_slot(descents, slots);
 }
 
 // One workgroup per tile of kExtractRankTile C entries.  mc > 0, nnz_c > 0.
@@ -241,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void extract_keys_kernel(int mc, int nnz_
     const long long last = (base + kWave < nnz_c ? base + kWave : nnz_c) - 1;
     const long long j = base + lane;
     if (j > last) continue;
-    const int i = extract_wave_row(c_rowptr, mc, base, last, j);
+    const int i = wave_row_of(c_rowptr, mc, base, last, j);
     keys[j] = static_cast<u64>(static_cast<unsigned>(i)) << col_bits | static_cast<unsigned>(c_colindex[j]);
   }
 }
@@ -300,14 +255,14 @@ void launch_extract_mark(hipStream_t stream, int mc, int m, const int *rows, int
   if (rows == nullptr && colmap == nullptr) return;
   const long long items = std::max(rows != nullptr ? static_cast<long long>(mc) : 0, colmap != nullptr ? static_cast<long long>(n) : 0);
   if (items <= 0) return;
-  SPMV_ACC_LAUNCH(extract_mark_kernel, dim3(extract_grid(items, kThreads)), dim3(kThreads), 0, stream, mc, m, rows, inv_row, n, nc, colmap, inv_col);
+  SPMV_ACC_LAUNCH(extract_mark_kernel, dim3(grid_for(items, kThreads)), dim3(kThreads), 0, stream, mc, m, rows, inv_row, n, nc, colmap, inv_col);
 }
 
 void launch_extract_census(hipStream_t stream, int mc, int m, int nnz_a, const int *rows, const int *a_rowptr, const int *inv_row, int n, int nc,
                            const int *colmap, const int *inv_col, int *len, unsigned *slots) {
   if (mc <= 0 || m <= 0) return;
   const long long items = std::max(static_cast<long long>(mc) + 1, colmap != nullptr ? static_cast<long long>(n) : 0);
-  SPMV_ACC_LAUNCH(extract_census_kernel, dim3(extract_census_grid(items, kThreads)), dim3(kThreads), 0, stream, mc, m, nnz_a, rows, a_rowptr, inv_row, n,
+  SPMV_ACC_LAUNCH(extract_census_kernel, dim3(census_grid_for(items, kThreads)), dim3(kThreads), 0, stream, mc, m, nnz_a, rows, a_rowptr, inv_row, n,
                   nc, colmap, inv_col, len, slots);
 }
 
@@ -323,45 +278,45 @@ bool launch_extract_scan_kept(hipStream_t stream, const int *newcol, size_t coun
 void launch_extract_candidates(hipStream_t stream, int mc, int nnz_a, int S, const int *rows, const int *a_rowptr, const int *a_colindex,
                                const int *src_ptr, int n, const int *colmap, int diag_lo, int diag_hi, int *newcol, unsigned *slots) {
   if (mc <= 0 || S <= 0) return;
-  SPMV_ACC_LAUNCH(extract_candidates_kernel, dim3(extract_census_grid(static_cast<long long>(S) + 1, kExtractRankTile)), dim3(kThreads), 0, stream, mc,
+  SPMV_ACC_LAUNCH(extract_candidates_kernel, dim3(census_grid_for(static_cast<long long>(S) + 1, kExtractRankTile)), dim3(kThreads), 0, stream, mc,
                   nnz_a, S, rows, a_rowptr, a_colindex, src_ptr, n, colmap, diag_lo, diag_hi, newcol, slots);
 }
 
 void launch_extract_rowptr(hipStream_t stream, int mc, const int *src_ptr, const int *pos, int *c_rowptr) {
   if (mc < 0) return;
-  SPMV_ACC_LAUNCH(extract_rowptr_kernel, dim3(extract_grid(static_cast<long long>(mc) + 1, kThreads)), dim3(kThreads), 0, stream, mc, src_ptr, pos,
+  SPMV_ACC_LAUNCH(extract_rowptr_kernel, dim3(grid_for(static_cast<long long>(mc) + 1, kThreads)), dim3(kThreads), 0, stream, mc, src_ptr, pos,
                   c_rowptr);
 }
 
 void launch_extract_scatter(hipStream_t stream, int mc, int nnz_a, int S, int cap, const int *rows, const int *a_rowptr, const int *src_ptr,
                             const int *newcol, const int *pos, int *c_colindex, int *map) {
   if (mc <= 0 || S <= 0 || cap <= 0) return;
-  SPMV_ACC_LAUNCH(extract_scatter_kernel, dim3(extract_grid(S, kExtractRankTile)), dim3(kThreads), 0, stream, mc, nnz_a, S, cap, rows, a_rowptr, src_ptr,
+  SPMV_ACC_LAUNCH(extract_scatter_kernel, dim3(grid_for(S, kExtractRankTile)), dim3(kThreads), 0, stream, mc, nnz_a, S, cap, rows, a_rowptr, src_ptr,
                   newcol, pos, c_colindex, map);
 }
 
 void launch_extract_descents(hipStream_t stream, int mc, int nnz_c, const int *c_rowptr, const int *c_colindex, unsigned *slots) {
   if (mc <= 0 || nnz_c <= 0) return;
-  SPMV_ACC_LAUNCH(extract_descents_kernel, dim3(extract_census_grid(nnz_c, kExtractRankTile)), dim3(kThreads), 0, stream, mc, nnz_c, c_rowptr, c_colindex,
+  SPMV_ACC_LAUNCH(extract_descents_kernel, dim3(census_grid_for(nnz_c, kExtractRankTile)), dim3(kThreads), 0, stream, mc, nnz_c, c_rowptr, c_colindex,
                   slots);
 }
 
 void launch_extract_keys(hipStream_t stream, int mc, int nnz_c, const int *c_rowptr, const int *c_colindex, int col_bits, unsigned long long *keys) {
   if (mc <= 0 || nnz_c <= 0) return;
-  SPMV_ACC_LAUNCH(extract_keys_kernel, dim3(extract_grid(nnz_c, kExtractRankTile)), dim3(kThreads), 0, stream, mc, nnz_c, c_rowptr, c_colindex, col_bits,
+  SPMV_ACC_LAUNCH(extract_keys_kernel, dim3(grid_for(nnz_c, kExtractRankTile)), dim3(kThreads), 0, stream, mc, nnz_c, c_rowptr, c_colindex, col_bits,
                   keys);
 }
 
 void launch_extract_sorted(hipStream_t stream, int nnz_c, const unsigned long long *keys, int col_bits, const int *order, const int *map_tmp,
                            int *c_colindex, int *map) {
   if (nnz_c <= 0) return;
-  SPMV_ACC_LAUNCH(extract_sorted_kernel, dim3(extract_grid(nnz_c, kThreads)), dim3(kThreads), 0, stream, nnz_c, nnz_c, keys, col_bits, order, map_tmp,
+  SPMV_ACC_LAUNCH(extract_sorted_kernel, dim3(grid_for(nnz_c, kThreads)), dim3(kThreads), 0, stream, nnz_c, nnz_c, keys, col_bits, order, map_tmp,
                   c_colindex, map);
 }
 
 void launch_extract_values(hipStream_t stream, int nnz_c, int nnz_a, const int *map, const double *a_value, double *value) {
   if (nnz_c <= 0) return;
-  SPMV_ACC_LAUNCH(extract_values_kernel, dim3(extract_grid(nnz_c, kExtractTile)), dim3(kThreads), 0, stream, nnz_c, nnz_a, map, a_value, value);
+  SPMV_ACC_LAUNCH(extract_values_kernel, dim3(grid_for(nnz_c, kExtractTile)), dim3(kThreads), 0, stream, nnz_c, nnz_a, map, a_value, value);
 }
 
 } // namespace spmv_acc

@@ -18,14 +18,13 @@
 //    in the scan -- inside row i of A, which the sorted key names, so a handful of steps in lines the neighbours share -- and t follows.  The
 //    pass rewrites the sort's order array in place as pa and writes pb.
 //
-// 4. Values (spgemm_values_kernel, the per-step hot path and the first call's last launch): coo_values_kernel's tiling and summation order, the
-//    gather replaced by two index loads, two gathers and a product rounded on its own (fp contraction is off in this file's sums: a fused
-//    multiply-add would round once where the definition rounds twice).  Streams start, pa and pb (4 B per entry, 8 B per product), gathers 16 B
+// 4. Values (spgemm_values_kernel, the per-step hot path and the first call's last launch): the body coo_values_kernel runs (structure_passes.hpp
+//    sum_runs: its tiling and summation order) on SpgemmTerms, the gather replaced by two index loads, two gathers and a product rounded on its
+//    own (fp contraction is off in the product and in the shared sums: a fused multiply-add would round once where the definition rounds twice).  Streams start, pa and pb (4 B per entry, 8 B per product), gathers 16 B
 //    per product, writes 8 B per entry.  Four entries per lane: spgemm.hpp kSpgemmPerLane.  The sums depend on the map and the values alone (no
 //    atomics), so the same values give the same bits.
 #include "spgemm.hpp"
-#include "device_utils.hpp"
-#include "kernels.hpp"
+#include "structure_passes.hpp"
 
 #include <rocprim/device/device_reduce.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -34,34 +33,12 @@ namespace spmv_acc {
 namespace {
 
 using namespace dev;
+using namespace passes;
 
 typedef unsigned long long u64;
 
-unsigned spgemm_grid(long long items, int per_block) {
-  long long b = (items + per_block - 1) / per_block;
-  const long long cap = max_grid_blocks();
-  return static_cast<unsigned>(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-// B's row c as positions [lo, lo + len) inside B's arrays, whatever b_rowptr holds (c has passed the census: 0 <= c < k)
-__device__ __forceinline__ int spgemm_b_row(const int *__restrict__ b_rowptr, int nnz_b, int c, int *len) {
-  int lo = b_rowptr[c], hi = b_rowptr[c + 1];
-  lo = lo < 0 ? 0 : (lo > nnz_b ? nnz_b : lo);
-  hi = hi < lo ? lo : (hi > nnz_b ? nnz_b : hi);
-  *len = hi - lo;
-  return lo;
-}
-
-// the largest q in [lo, hi] with off[q] <= e (lo itself if there is none).  off ascends; with off[lo] <= e < off[hi + 1] this is the non-zero of
-// A whose products include e: non-zeros without products (off[q] == off[q + 1]) are passed over
-__device__ __forceinline__ int spgemm_holder(const long long *__restrict__ off, int lo, int hi, long long e) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (off[mid] <= e) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
+// (last_at_most in the scan `off`: the non-zero of A whose products include e; non-zeros without products, off[q] == off[q + 1], are passed over.
+// A column of A names a row of B: it has passed the census, 0 <= c < k, and row_extent holds the row inside B's arrays)
 
 __global__ __launch_bounds__(kThreads) void spgemm_counts_kernel(int m, int nnz_a, const int *__restrict__ a_rowptr,
                                                                  const int *__restrict__ a_colindex, const int *__restrict__ b_rowptr, int nnz_b,
@@ -72,18 +49,10 @@ __global__ __launch_bounds__(kThreads) void spgemm_counts_kernel(int m, int nnz_
       count[q] = 0; // (the scan's closing element)
       continue;
     }
-    int len;
-    (void)spgemm_b_row(b_rowptr, nnz_b, a_colindex[q], &len);
-    count[q] = len;
-    if (arow != nullptr) { // the last row r in [0, m) with a_rowptr[r] <= q: the search stays inside a_rowptr[0 .. m) whatever it holds
-      int lo = 0, hi = m - 1;
-      while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (a_rowptr[mid] <= q) lo = mid;
-        else hi = mid - 1;
-      }
-      arow[q] = lo;
-    }
+    int hi;
+    const int lo = row_extent(b_rowptr, nnz_b, a_colindex[q], &hi);
+    count[q] = hi - lo;
+    if (arow != nullptr) arow[q] = last_at_most(a_rowptr, 0, m - 1, q); // (stays inside a_rowptr[0 .. m) whatever it holds)
   }
 }
 
@@ -100,15 +69,16 @@ __global__ __launch_bounds__(kThreads) void spgemm_expand_kernel(int nnz_a, int 
     if (base >= nprod) continue; // (wave-uniform)
     const long long last = (base + kSpgemmExpandChunk < nprod ? base + kSpgemmExpandChunk : nprod) - 1;
     // the non-zeros of A that hold the wavefront's first and last product (every lane the same search), then each lane's between them
-    const int q_first = spgemm_holder(off, 0, nnz_a - 1, base);
-    const int q_last = spgemm_holder(off, q_first, nnz_a - 1, last);
+    int q_last;
+    const int q_first = wave_end_rows(off, nnz_a, base, last, &q_last);
 #pragma unroll
     for (int k = 0; k < kSpgemmExpandPerLane; ++k) {
       const long long e = base + k * kWave + lane;
       if (e > last) continue;
-      const int q = spgemm_holder(off, q_first, q_last, e);
-      int len;
-      const int lo = spgemm_b_row(b_rowptr, nnz_b, a_colindex[q], &len);
+      const int q = last_at_most(off, q_first, q_last, e);
+      int hi;
+      const int lo = row_extent(b_rowptr, nnz_b, a_colindex[q], &hi);
+      const int len = hi - lo;
       long long step = e - off[q]; // (0 <= step < len by the scan; held to it so that no array content can move t outside B's arrays)
       step = step >= len ? len - 1 : step;
       const int t = lo + static_cast<int>(step < 0 ? 0 : step);
@@ -131,9 +101,10 @@ __global__ __launch_bounds__(kThreads) void spgemm_map_kernel(int m, int nnz_a, 
     int lo = a_rowptr[i], hi = a_rowptr[i + 1] - 1; // row i of A, held inside A's arrays
     lo = lo < 0 ? 0 : (lo > nnz_a - 1 ? nnz_a - 1 : lo);
     hi = hi < lo ? lo : (hi > nnz_a - 1 ? nnz_a - 1 : hi);
-    const int q = spgemm_holder(off, lo, hi, e); // (with an a_rowptr that does not ascend: some non-zero of A, and t below is held inside B)
-    int len;
-    const int b_lo = spgemm_b_row(b_rowptr, nnz_b, a_colindex[q], &len);
+    const int q = last_at_most(off, lo, hi, e); // (with an a_rowptr that does not ascend: some non-zero of A, and t below is held inside B)
+    int b_hi;
+    const int b_lo = row_extent(b_rowptr, nnz_b, a_colindex[q], &b_hi);
+    const int len = b_hi - b_lo;
     long long step = e - off[q];
     step = step >= len ? len - 1 : step;
     const int t = b_lo + static_cast<int>(step < 0 ? 0 : step);
@@ -142,107 +113,41 @@ __global__ __launch_bounds__(kThreads) void spgemm_map_kernel(int m, int nnz_a, 
   }
 }
 
-// the rounded product of sorted position p (0 <= p < nprod).  The map is the caller's and carries no lengths: pa / pb are not checked
-__device__ __forceinline__ double spgemm_fetch(const int *__restrict__ pa, const int *__restrict__ pb, const double *__restrict__ a,
-                                               const double *__restrict__ b, int p) {
+// the terms of the product's runs: the rounded product of sorted position p (0 <= p < nprod).  The map is the caller's and carries no lengths:
+// pa / pb are not checked
+struct SpgemmTerms {
+  struct Pair {
+    int a, b;
+  };
+  struct Factors {
+    double a, b;
+  };
+  const int *__restrict__ pa;
+  const int *__restrict__ pb;
+  const double *__restrict__ a_value;
+  const double *__restrict__ b_value;
+  __device__ __forceinline__ Pair index(int p) const { return {pa[p], pb[p]}; }
+  __device__ __forceinline__ Factors load(Pair u) const { return {a_value[u.a], b_value[u.b]}; }
+  __device__ __forceinline__ double term(Pair, Factors v) const {
 #pragma clang fp contract(off)
-  const double prod = a[pa[p]] * b[pb[p]];
-  return prod;
-}
-
-// the wavefront form of coo.hpp's order for the run [s, end), end - s > 64.  All 64 lanes must call it; every lane returns the sum.
-__device__ __forceinline__ double spgemm_wave_run_sum(const int *__restrict__ pa, const int *__restrict__ pb, const double *__restrict__ a,
-                                                      const double *__restrict__ b, int s, int end, int lane) {
-#pragma clang fp contract(off)
-  int p = s + lane;
-  double part = spgemm_fetch(pa, pb, a, b, p);
-  p += kWave;
-  for (; p + 3 * kWave < end; p += 4 * kWave) { // four independent products in flight, added in order
-    const double v0 = spgemm_fetch(pa, pb, a, b, p), v1 = spgemm_fetch(pa, pb, a, b, p + kWave);
-    const double v2 = spgemm_fetch(pa, pb, a, b, p + 2 * kWave), v3 = spgemm_fetch(pa, pb, a, b, p + 3 * kWave);
-    part += v0;
-    part += v1;
-    part += v2;
-    part += v3;
+    const double prod = v.a * v.b; // rounded here, added by the caller
+    return prod;
   }
-  for (; p < end; p += kWave) part += spgemm_fetch(pa, pb, a, b, p);
-  return group_sum<64>(part);
-}
+  __device__ __forceinline__ double fetch(int p) const {
+    const Pair u = index(p);
+    return term(u, load(u));
+  }
+};
+
+static_assert(kSpgemmWaveChunk == kWave * kSpgemmPerLane && kSpgemmTile == (kThreads / kWave) * kSpgemmWaveChunk,
+              "sum_runs derives its tile from kSpgemmPerLane");
 
 // One workgroup per tile of kSpgemmTile C entries, blocks stride over the tiles beyond the grid.  nprod > 0 (the launcher checks).
 // (waves_per_eu: the kernel asks for the eighth wave per SIMD; the compiler then orders the loads to fit 64 VGPRs without scratch)
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void spgemm_values_kernel(int nprod, int nnz_c, const int *__restrict__ pa, const int *__restrict__ pb,
                                                                  const int *__restrict__ start, const double *__restrict__ a_value,
                                                                  const double *__restrict__ b_value, double *__restrict__ value) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const long long ntiles = (static_cast<long long>(nnz_c) + kSpgemmTile - 1) / kSpgemmTile;
-  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) { // (block-uniform)
-    const long long base = tile * kSpgemmTile + static_cast<long long>(wave) * kSpgemmWaveChunk;
-    if (base >= nnz_c) continue; // (wave-uniform)
-    int s[kSpgemmPerLane];
-    int len[kSpgemmPerLane]; // the run's length; NEGATED where it is longer than kCooLongRun (such a run sits the lane pass out)
-    double acc[kSpgemmPerLane];
-    int rounds = 0;
-    bool any_long = false;
-#pragma unroll
-    for (int k = 0; k < kSpgemmPerLane; ++k) {
-      const long long j = base + k * kWave + lane;
-      int a = 0, b = 0;
-      if (j < nnz_c) {
-        a = load_stream(start + j);
-        b = load_stream(start + j + 1);
-      }
-      a = a < 0 ? 0 : (a > nprod ? nprod : a); // the map is the CALLER's array here: every run is clamped to [0, nprod]
-      b = b < a ? a : (b > nprod ? nprod : b);
-      s[k] = a;
-      const int l = b - a;
-      len[k] = l > kCooLongRun ? -l : l;
-      any_long |= l > kCooLongRun;
-      rounds = l <= kCooLongRun && l > rounds ? l : rounds;
-      acc[k] = 0.0; // (an empty run -- a crafted map -- sums to 0.0)
-    }
-    for (int t = 0; t < rounds; ++t) {
-      int ua[kSpgemmPerLane], ub[kSpgemmPerLane];
-      double va[kSpgemmPerLane], vb[kSpgemmPerLane];
-#pragma unroll
-      for (int k = 0; k < kSpgemmPerLane; ++k) {
-        const int p = t < len[k] ? s[k] + t : 0;
-        ua[k] = pa[p];
-        ub[k] = pb[p];
-      }
-#pragma unroll
-      for (int k = 0; k < kSpgemmPerLane; ++k) {
-        va[k] = a_value[ua[k]];
-        vb[k] = b_value[ub[k]];
-      }
-#pragma unroll
-      for (int k = 0; k < kSpgemmPerLane; ++k) {
-        const double vk = va[k] * vb[k]; // rounded here, added below
-        acc[k] = t < len[k] ? (t == 0 ? vk : acc[k] + vk) : acc[k];
-      }
-    }
-    if (__ballot(any_long)) { // (wave-uniform; never taken on a mesh)
-#pragma unroll
-      for (int k = 0; k < kSpgemmPerLane; ++k) {
-        unsigned long long todo = __ballot(len[k] < 0);
-        while (todo) { // the wavefront takes its long runs one at a time, in lane order
-          const int owner = __ffsll(static_cast<long long>(todo)) - 1;
-          todo &= todo - 1;
-          const int a = __shfl(s[k], owner, kWave);
-          const int l = -__shfl(len[k], owner, kWave);
-          const double sum = spgemm_wave_run_sum(pa, pb, a_value, b_value, a, a + l, lane);
-          if (lane == owner) acc[k] = sum;
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kSpgemmPerLane; ++k) {
-      const long long j = base + k * kWave + lane;
-      if (j < nnz_c) value[j] = acc[k];
-    }
-  }
+  sum_runs<kSpgemmPerLane>(nprod, nnz_c, start, SpgemmTerms{pa, pb, a_value, b_value}, value);
 }
 
 } // namespace
@@ -250,7 +155,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))
 void launch_spgemm_counts(hipStream_t stream, int m, int nnz_a, const int *a_rowptr, const int *a_colindex, const int *b_rowptr, int nnz_b,
                           long long *count, int *arow) {
   if (nnz_a <= 0 || m <= 0) return;
-  SPMV_ACC_LAUNCH(spgemm_counts_kernel, dim3(spgemm_grid(static_cast<long long>(nnz_a) + 1, kThreads)), dim3(kThreads), 0, stream, m, nnz_a,
+  SPMV_ACC_LAUNCH(spgemm_counts_kernel, dim3(grid_for(static_cast<long long>(nnz_a) + 1, kThreads)), dim3(kThreads), 0, stream, m, nnz_a,
                   a_rowptr, a_colindex, b_rowptr, nnz_b, count, arow);
 }
 
@@ -266,21 +171,21 @@ bool launch_spgemm_scan(hipStream_t stream, const long long *count, int nnz_a, l
 void launch_spgemm_expand(hipStream_t stream, int nnz_a, int nprod, const long long *off, const int *arow, const int *a_colindex,
                           const int *b_rowptr, int nnz_b, const int *b_colindex, int col_bits, unsigned long long *keys) {
   if (nnz_a <= 0 || nnz_b <= 0 || nprod <= 0) return;
-  SPMV_ACC_LAUNCH(spgemm_expand_kernel, dim3(spgemm_grid(nprod, kSpgemmExpandTile)), dim3(kThreads), 0, stream, nnz_a, nprod, off, arow,
+  SPMV_ACC_LAUNCH(spgemm_expand_kernel, dim3(grid_for(nprod, kSpgemmExpandTile)), dim3(kThreads), 0, stream, nnz_a, nprod, off, arow,
                   a_colindex, b_rowptr, nnz_b, b_colindex, col_bits, keys);
 }
 
 void launch_spgemm_map(hipStream_t stream, int m, int nnz_a, int nprod, const unsigned long long *keys, int col_bits, const long long *off,
                        const int *a_rowptr, const int *a_colindex, const int *b_rowptr, int nnz_b, int *pa, int *pb) {
   if (m <= 0 || nnz_a <= 0 || nnz_b <= 0 || nprod <= 0) return;
-  SPMV_ACC_LAUNCH(spgemm_map_kernel, dim3(spgemm_grid(nprod, kThreads)), dim3(kThreads), 0, stream, m, nnz_a, nprod, keys, col_bits, off,
+  SPMV_ACC_LAUNCH(spgemm_map_kernel, dim3(grid_for(nprod, kThreads)), dim3(kThreads), 0, stream, m, nnz_a, nprod, keys, col_bits, off,
                   a_rowptr, a_colindex, b_rowptr, nnz_b, pa, pb);
 }
 
 void launch_spgemm_values(hipStream_t stream, int nprod, int nnz_c, const int *pa, const int *pb, const int *start, const double *a_value,
                           const double *b_value, double *value) {
   if (nnz_c <= 0 || nprod <= 0) return;
-  SPMV_ACC_LAUNCH(spgemm_values_kernel, dim3(spgemm_grid(nnz_c, kSpgemmTile)), dim3(kThreads), 0, stream, nprod, nnz_c, pa, pb, start, a_value,
+  SPMV_ACC_LAUNCH(spgemm_values_kernel, dim3(grid_for(nnz_c, kSpgemmTile)), dim3(kThreads), 0, stream, nprod, nnz_c, pa, pb, start, a_value,
                   b_value, value);
 }
 

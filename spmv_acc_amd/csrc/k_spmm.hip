@@ -16,14 +16,14 @@
 //   * rows longer than kSpmmLongRow (hub rows): the two kernels above skip them.  The plan cuts them into pieces of kSpmmPiece non-zeros
 //     (spmm.cpp); spmm_pieces_kernel gives each piece a wavefront that writes the piece's partial k-vector to plan scratch, and
 //     spmm_fixup_kernel adds a row's pieces in piece order and applies alpha / beta -- the plus_kernel + plus_fixup_kernel pattern.
-#include "device_utils.hpp"
-#include "kernels.hpp"
 #include "spmm.hpp"
+#include "structure_passes.hpp"
 
 namespace spmv_acc {
 namespace {
 
 using namespace dev;
+using passes::grid_for; // (the launchers' clamped grid)
 
 // (the size rules themselves are in spmm.hpp; the constants here are geometry)
 constexpr int kSpmmTeamMax = kSpmmPanel / 2; // lanes of the widest team: two columns per lane
@@ -275,12 +275,6 @@ __global__ __launch_bounds__(kThreads) void spmm_scale_kernel(long long m, int k
     double *yp = y + r * syi + c * syj;
     *yp = beta == 0.0 ? 0.0 : beta * *yp;
   }
-}
-
-unsigned grid_for(long long items, int per_block) {
-  long long b = (items + per_block - 1) / per_block;
-  const long long cap = max_grid_blocks();
-  return static_cast<unsigned>(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
 template <int TS, bool SINGLE = false>

@@ -16,8 +16,7 @@
 //    of its 512 non-zeros' ends by binary search in rowptr and each lane its non-zeros' rows between them.  The adds are vector
 //    global_atomic_add_f64 without return (no compare-and-swap loop: tests/test_transpose_host.py reads the assembly).  This is the one kernel
 //    of the library whose sums depend on arrival order.  Every column is checked against n before it becomes an address.
-#include "device_utils.hpp"
-#include "kernels.hpp"
+#include "structure_passes.hpp"
 #include "transpose.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -27,23 +26,7 @@ namespace spmv_acc {
 namespace {
 
 using namespace dev;
-
-unsigned trans_grid(long long items, int per_block) {
-  long long b = (items + per_block - 1) / per_block;
-  const long long cap = max_grid_blocks();
-  return static_cast<unsigned>(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-// largest r in [lo, hi] with rp[r] <= q (lo where there is none): the row that holds non-zero q when rp[lo] <= q < rp[hi + 1].  Stays inside
-// [lo, hi] whatever rp holds.
-__device__ __forceinline__ int row_holding(const int *__restrict__ rp, int lo, int hi, int q) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (rp[mid] <= q) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
+using namespace passes;
 
 __global__ __launch_bounds__(kThreads) void transpose_check_kernel(const int *__restrict__ ci, int nnz, int n, unsigned *__restrict__ bad) {
   const long long stride = static_cast<long long>(gridDim.x) * kThreads;
@@ -55,21 +38,13 @@ __global__ __launch_bounds__(kThreads) void transpose_check_kernel(const int *__
 
 __global__ __launch_bounds__(kThreads) void transpose_rowptr_kernel(const int *__restrict__ keys, int nnz, int n, int *__restrict__ t_rowptr) {
   const long long stride = static_cast<long long>(gridDim.x) * kThreads;
-  for (long long c = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; c <= n; c += stride) {
-    int lo = 0, hi = nnz; // first p in [0, nnz] with keys[p] >= c
-    while (lo < hi) {
-      const int mid = lo + (hi - lo) / 2;
-      if (keys[mid] < c) lo = mid + 1;
-      else hi = mid;
-    }
-    t_rowptr[c] = lo;
-  }
+  for (long long c = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; c <= n; c += stride) t_rowptr[c] = first_at_least(keys, 0, nnz, c);
 }
 
 __global__ __launch_bounds__(kThreads) void transpose_rows_kernel(const int *__restrict__ rp, int m, int nnz, int *__restrict__ row_of) {
   const long long stride = static_cast<long long>(gridDim.x) * kThreads;
   for (long long q = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; q < nnz; q += stride)
-    row_of[q] = row_holding(rp, 0, m - 1, static_cast<int>(q));
+    row_of[q] = last_at_most(rp, 0, m - 1, static_cast<int>(q));
 }
 
 __global__ __launch_bounds__(kThreads) void transpose_gather_kernel(int nnz, const int *__restrict__ perm, const int *__restrict__ row_of,
@@ -128,14 +103,14 @@ __global__ __launch_bounds__(kThreads) void spmv_t_scatter_kernel(int m, int n, 
     }
     // the rows of the wavefront's first and last non-zero (every lane the same search), then each non-zero's row between them: a wavefront inside
     // one long row searches nothing, 512 non-zeros of 3 per row take 8 steps in lines the whole wavefront shares
-    const int r_first = row_holding(rp, 0, m - 1, static_cast<int>(b));
-    const int r_last = row_holding(rp, r_first, m - 1, static_cast<int>(e - 1));
+    int r_last;
+    const int r_first = wave_end_rows(rp, m, static_cast<int>(b), static_cast<int>(e - 1), &r_last);
     int xrow = -1;
     double xr = 0.0;
 #pragma unroll
     for (int k = 0; k < kTransPerLane; ++k) {
       if (!in[k]) continue;
-      const int row = row_holding(rp, r_first, r_last, static_cast<int>(base + k * kWave + lane));
+      const int row = last_at_most(rp, r_first, r_last, static_cast<int>(base + k * kWave + lane));
       if (row != xrow) { // x[row] once per piece of a row
         xr = x[row];
         xrow = row;
@@ -149,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void spmv_t_scatter_kernel(int m, int n, 
 
 void launch_transpose_check(hipStream_t stream, const int *ci, int nnz, int n, unsigned *bad) {
   if (nnz <= 0) return;
-  SPMV_ACC_LAUNCH(transpose_check_kernel, dim3(trans_grid(nnz, 4 * kThreads)), dim3(kThreads), 0, stream, ci, nnz, n, bad);
+  SPMV_ACC_LAUNCH(transpose_check_kernel, dim3(grid_for(nnz, 4 * kThreads)), dim3(kThreads), 0, stream, ci, nnz, n, bad);
 }
 
 bool launch_transpose_sort(hipStream_t stream, const int *ci, int nnz, int n, int *keys_out, int *perm, void *tmp, size_t *tmp_bytes) {
@@ -158,37 +133,37 @@ bool launch_transpose_sort(hipStream_t stream, const int *ci, int nnz, int n, in
 }
 
 void launch_transpose_rowptr(hipStream_t stream, const int *keys, int nnz, int n, int *t_rowptr) {
-  SPMV_ACC_LAUNCH(transpose_rowptr_kernel, dim3(trans_grid(static_cast<long long>(n) + 1, kThreads)), dim3(kThreads), 0, stream, keys, nnz, n,
+  SPMV_ACC_LAUNCH(transpose_rowptr_kernel, dim3(grid_for(static_cast<long long>(n) + 1, kThreads)), dim3(kThreads), 0, stream, keys, nnz, n,
                   t_rowptr);
 }
 
 void launch_transpose_rows(hipStream_t stream, const int *rp, int m, int nnz, int *row_of) {
   if (nnz <= 0 || m <= 0) return;
-  SPMV_ACC_LAUNCH(transpose_rows_kernel, dim3(trans_grid(nnz, kThreads)), dim3(kThreads), 0, stream, rp, m, nnz, row_of);
+  SPMV_ACC_LAUNCH(transpose_rows_kernel, dim3(grid_for(nnz, kThreads)), dim3(kThreads), 0, stream, rp, m, nnz, row_of);
 }
 
 void launch_transpose_gather(hipStream_t stream, int nnz, const int *perm, const int *row_of, const double *value, int *t_colindex,
                              double *t_value) {
   if (nnz <= 0) return;
-  SPMV_ACC_LAUNCH(transpose_gather_kernel, dim3(trans_grid(nnz, kThreads)), dim3(kThreads), 0, stream, nnz, perm, row_of, value, t_colindex,
+  SPMV_ACC_LAUNCH(transpose_gather_kernel, dim3(grid_for(nnz, kThreads)), dim3(kThreads), 0, stream, nnz, perm, row_of, value, t_colindex,
                   t_value);
 }
 
 void launch_transpose_values(hipStream_t stream, int nnz, const int *perm, const double *value, double *t_value) {
   if (nnz <= 0) return;
-  SPMV_ACC_LAUNCH(transpose_values_kernel, dim3(trans_grid(nnz, kThreads)), dim3(kThreads), 0, stream, nnz, perm, value, t_value);
+  SPMV_ACC_LAUNCH(transpose_values_kernel, dim3(grid_for(nnz, kThreads)), dim3(kThreads), 0, stream, nnz, perm, value, t_value);
 }
 
 void launch_spmv_t_scale(hipStream_t stream, int n, double beta, double *y) {
   if (n <= 0) return;
-  SPMV_ACC_LAUNCH(spmv_t_scale_kernel, dim3(trans_grid(n, kThreads)), dim3(kThreads), 0, stream, n, beta, y);
+  SPMV_ACC_LAUNCH(spmv_t_scale_kernel, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, n, beta, y);
 }
 
 void launch_spmv_t_scatter(hipStream_t stream, int m, int n, int nnz_end, double alpha, const int *rp, const int *ci, const double *v,
                            const double *x, double *y) {
   if (m <= 0 || n <= 0 || nnz_end <= 0) return;
   // (a grid for every tile up to nnz_end: the tiles below the view's first non-zero do not exist for the kernel, their blocks leave at once)
-  SPMV_ACC_LAUNCH(spmv_t_scatter_kernel, dim3(trans_grid(nnz_end, kTransTile)), dim3(kThreads), 0, stream, m, n, nnz_end, alpha, rp, ci, v, x, y);
+  SPMV_ACC_LAUNCH(spmv_t_scatter_kernel, dim3(grid_for(nnz_end, kTransTile)), dim3(kThreads), 0, stream, m, n, nnz_end, alpha, rp, ci, v, x, y);
 }
 
 } // namespace spmv_acc

@@ -17,6 +17,7 @@ import spmv_acc_amd
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
 NEW_SOURCES = ("coo.hpp", "k_coo.hip", "coo.cpp")
+SHARED = "structure_passes.hpp"  # what the structure-pass kernel files share: the other features' tables name it too
 LONG_RUN = 64  # kCooLongRun (test_coo_size_rules_name_their_tests holds the two together)
 
 # (rule, file, regex that must match the source, GPU tests of tests/test_gpu_coo.py that cross it at test size, what it selects)
@@ -36,14 +37,22 @@ COO_SIZE_RULES = [
      "range census: at most 1 024 workgroups (more than 1 Mi triples stride: the 3.2 M case), one count slot per wavefront"),
     ("kCooCheckSlots", CSRC + "coo.hpp", r"constexpr int kCooCheckSlots = 4 \* kCooCheckBlocks;",
      ["test_coo_contract"], "the host adds up every slot, written or not (small inputs leave most at zero)"),
-    ("kMaxGridBlocks (grid striding)", CSRC + "k_coo.hip", r"const long long cap = max_grid_blocks\(\);",
+    ("kMaxGridBlocks (grid striding)", CSRC + SHARED, r"const long long cap = max_grid_blocks\(\);",
      ["test_coo_grid_stride_at_test_size"], "every kernel of the two entries strides over the work beyond max_grid_blocks() workgroups"),
-    ("tile loop of the summing pass", CSRC + "k_coo.hip", r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\)",
+    ("kMaxGridBlocks (grid striding): the assembly's call", CSRC + "k_coo.hip", r"dim3\(grid_for\(nnz, kCooTile\)\)",
+     ["test_coo_grid_stride_at_test_size"], "the launchers of the two entries take the shared grid"),
+    ("tile loop of the summing pass", CSRC + SHARED, r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\)",
      ["test_coo_grid_stride_at_test_size"], "blocks stride over the tiles of CSR entries beyond the grid"),
-    ("long runs leave the lane pass", CSRC + "k_coo.hip", r"len\[k\] = l > kCooLongRun \? -l : l;",
+    ("tile loop of the summing pass: the assembly's tile", CSRC + "k_coo.hip", r"kCooTile == \(kThreads / kWave\) \* kCooWaveChunk, \"sum_runs derives",
+     ["test_coo_grid_stride_at_test_size"], "the shared loop's tile is the launcher's kCooTile"),
+    ("long runs leave the lane pass", CSRC + SHARED, r"len\[k\] = l > kCooLongRun \? -l : l;",
      ["test_assembly_is_the_host_stable_sort", "test_reassembly_follows_new_values"], "a run of 65 or more is summed by the wavefront, one run at a time"),
-    ("four gathers per step of a long run", CSRC + "k_coo.hip", r"for \(; p \+ 3 \* kWave < end; p \+= 4 \* kWave\)",
+    ("long runs leave the lane pass: the assembly's call", CSRC + "k_coo.hip", r"sum_runs<kCooPerLane>\(nnz_coo, nnz, start, CooTerms\{order, val, nnz_coo\}, value\);",
+     ["test_assembly_is_the_host_stable_sort", "test_reassembly_follows_new_values"], "the summing pass is the shared body on the assembly's terms"),
+    ("four gathers per step of a long run", CSRC + SHARED, r"for \(; p \+ 3 \* kWave < end; p \+= 4 \* kWave\)",
      ["test_assembly_is_the_host_stable_sort"], "long runs: steps of four values per lane, then single ones (65: neither, 5 000: both)"),
+    ("four gathers per step of a long run: the assembly's gather", CSRC + "k_coo.hip", r"__device__ __forceinline__ double fetch\(int p\) const \{",
+     ["test_assembly_is_the_host_stable_sort"], "what a lane of the long-run path fetches per position: one checked gather"),
     ("key bits from m and n", CSRC + "coo.hpp", r"while \(bits < 31 && \(1LL << bits\) < n\) \+\+bits;",
      ["test_assembly_is_the_host_stable_sort"], "radix-sort passes follow the shape: 1 x 1 sorts 2 bits, 70 000 x 70 000 sorts 34 (more than 32), 200 000 x 150 000 sorts 36"),
     ("sort size paths", CSRC + "k_coo.hip", r"rocprim::radix_sort_pairs\(tmp, \*tmp_bytes, keys, keys_out, rocprim::counting_iterator<int>\(0\), order,",
@@ -71,7 +80,7 @@ def test_coo_size_rules_name_their_tests():
             assert t in defined, f"{name}: names {t}, which is not a test of tests/test_gpu_coo.py"
     # every named constant of the new files is registered above (tests/size_thresholds.py does not scan them)
     registered = " ".join(r[0] + " " + r[2] for r in COO_SIZE_RULES)
-    for f in NEW_SOURCES:
+    for f in NEW_SOURCES + (SHARED,):  # (the shared header holds none today)
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             assert k in registered, f"{f}: constant {k} is not in COO_SIZE_RULES"
     assert f"constexpr int kCooLongRun = {LONG_RUN};" in open(os.path.join(ROOT, CSRC, "coo.hpp")).read()

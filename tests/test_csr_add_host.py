@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
-from test_coo_host import _FakeTensor, _f, _i
+from test_coo_host import SHARED, _FakeTensor, _f, _i
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -37,8 +37,10 @@ CSR_ADD_SIZE_RULES = [
      [STRIDE], "blocks stride over the tiles of non-zeros beyond the grid, at most kCooCheckBlocks of them (large: 800 000 non-zeros, 3 125 tiles)"),
     ("row loop of the census", CSRC + "k_csr_add.hip", r"r < m; r \+= stride\)",
      [STRIDE, "test_csr_add_contract"], "rowptr extents, one row per lane, striding (large: 200 000 rows)"),
-    ("census grid", CSRC + "k_csr_add.hip", r"grid = grid > static_cast<unsigned>\(kCooCheckBlocks\) \? static_cast<unsigned>\(kCooCheckBlocks\) : grid;",
+    ("census grid", CSRC + SHARED, r"return grid > static_cast<unsigned>\(kCooCheckBlocks\) \? static_cast<unsigned>\(kCooCheckBlocks\) : grid;",
      [GPU, "test_csr_add_contract"], "one count slot per wavefront of at most 1 024 workgroups (hub_rows and large exceed them)"),
+    ("census grid: the add's call", CSRC + "k_csr_add.hip", r"dim3\(census_grid_for\(items, kCsrAddRankTile\), 2\)",
+     [GPU, "test_csr_add_contract"], "the census of both matrices takes the shared census grid"),
     ("tile loop of the match", CSRC + "k_csr_add.hip", r"if \(base >= items\) continue; // \(wave-uniform\)",
      [STRIDE], "nnz_a + 1 items: the closing element may open a tile of its own (nnz_a a multiple of 256)"),
     ("tile loop of A's places", CSRC + "k_csr_add.hip", r"const long long q = tile \* kCsrAddRankTile \+ threadIdx\.x;",
@@ -50,8 +52,10 @@ CSR_ADD_SIZE_RULES = [
      [STRIDE], "blocks stride over the tiles of C entries beyond the grid"),
     ("row pointer pass", CSRC + "k_csr_add.hip", r"r <= m; r \+= stride\)",
      [STRIDE], "one lane per row, striding (large: 200 001 rows, 782 workgroups)"),
-    ("kMaxGridBlocks (grid striding)", CSRC + "k_csr_add.hip", r"const long long cap = max_grid_blocks\(\);",
+    ("kMaxGridBlocks (grid striding)", CSRC + SHARED, r"const long long cap = max_grid_blocks\(\);",
      [STRIDE], "every kernel of the two entries strides over the work beyond max_grid_blocks() workgroups"),
+    ("kMaxGridBlocks (grid striding): the add's call", CSRC + "k_csr_add.hip", r"dim3\(grid_for\(nnz_c, kCsrAddTile\)\)",
+     [STRIDE], "the launchers of the two entries take the shared grid"),
     ("absent side of an entry", CSRC + "k_csr_add.hip", r"value\[j\] = has_a \? \(has_b \? both : ta\) : \(has_b \? tb : 0\.0\);",
      [GPU, "test_special_values", "test_csr_add_contract"], "both / only A / only B / neither (a crafted map): a select, never + 0.0"),
     ("scan sizes", CSRC + "k_csr_add.hip", r"ms, 0, static_cast<size_t>\(nnz_a\) \+ 1,",

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
-from test_coo_host import _FakeTensor, _f, _i
+from test_coo_host import SHARED, _FakeTensor, _f, _i
 from test_csr_add_host import dense_of, random_sorted_csr, same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,8 +40,10 @@ EXTRACT_SIZE_RULES = [
      [GPU], "workspace parts are padded to 256 B (counts that are no multiple of 64: most cases)"),
     ("kExtractCounts", CSRC + "extract.cpp", r"constexpr int kExtractCounts = 7;",
      [GPU, CONTRACT], "seven groups of per-wavefront counts: the census' five, the candidates' columns, the descents"),
-    ("census grid", CSRC + "k_extract.hip", r"return grid > static_cast<unsigned>\(kCooCheckBlocks\) \? static_cast<unsigned>\(kCooCheckBlocks\) : grid;",
+    ("census grid", CSRC + SHARED, r"return grid > static_cast<unsigned>\(kCooCheckBlocks\) \? static_cast<unsigned>\(kCooCheckBlocks\) : grid;",
      [STRIDE, CONTRACT], "one count slot per wavefront of at most 1 024 workgroups (large: 3 126 tiles of candidates exceed them)"),
+    ("census grid: the extraction's call", CSRC + "k_extract.hip", r"dim3\(census_grid_for\(static_cast<long long>\(S\) \+ 1, kExtractRankTile\)\)",
+     [STRIDE, CONTRACT], "the census, the candidates and the descents take the shared census grid"),
     ("row loop of the marks", CSRC + "k_extract.hip", r"for \(long long i = first; i < mc; i \+= stride\) \{",
      [STRIDE], "one selected row per lane, striding (large: 200 000 rows, 782 workgroups); likewise the columns: c < n; c += stride"),
     ("row loop of the census", CSRC + "k_extract.hip", r"for \(long long i = first; i <= mc; i \+= stride\) \{",
@@ -59,8 +61,10 @@ EXTRACT_SIZE_RULES = [
      [STRIDE], "one lane per row, striding (large: 200 001 rows)"),
     ("sorted pass", CSRC + "k_extract.hip", r"j < nnz_c; j \+= stride\) \{",
      [STRIDE], "one sorted entry per lane, striding (large: 3 125 workgroups)"),
-    ("kMaxGridBlocks (grid striding)", CSRC + "k_extract.hip", r"const long long cap = max_grid_blocks\(\);",
+    ("kMaxGridBlocks (grid striding)", CSRC + SHARED, r"const long long cap = max_grid_blocks\(\);",
      [STRIDE], "every kernel of the two entries strides over the work beyond max_grid_blocks() workgroups"),
+    ("kMaxGridBlocks (grid striding): the extraction's call", CSRC + "k_extract.hip", r"dim3\(grid_for\(nnz_c, kExtractTile\)\)",
+     [STRIDE], "the launchers of the two entries take the shared grid"),
     ("sort or not", CSRC + "extract.cpp", r"if \(descents != 0\) \{ // some row is not ascending: one stable sort by \(row, column\)",
      [GPU, STRIDE], "no descent inside a row (identity, sub_block, rows_shuffled, embed, tril, strict_triu, diag): the compaction is the answer; "
                     "otherwise (unsorted_in, repeats, permuted, band_after_map, hub_row, large) one radix sort"),

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
-from test_coo_host import LONG_RUN, _FakeTensor, _f, _i, coo_sum_model
+from test_coo_host import LONG_RUN, SHARED, _FakeTensor, _f, _i, coo_sum_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -37,14 +37,22 @@ SPGEMM_SIZE_RULES = [
      [GPU, "test_spgemm_grid_stride_at_test_size"], "products per workgroup: 1 024; a B row of 20 000 entries is 20 tiles"),
     ("tile loop of the expansion", CSRC + "k_spgemm.hip", r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\) \{ // \(block-uniform\)\n    const long long base = tile \* kSpgemmExpandTile",
      ["test_spgemm_grid_stride_at_test_size"], "blocks stride over the tiles of products beyond the grid"),
-    ("tile loop of the values pass", CSRC + "k_spgemm.hip", r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\) \{ // \(block-uniform\)\n    const long long base = tile \* kSpgemmTile",
+    ("tile loop of the values pass", CSRC + SHARED, r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\) \{ // \(block-uniform\)\n    const long long base = tile \* tile_items",
      ["test_spgemm_grid_stride_at_test_size"], "blocks stride over the tiles of C entries beyond the grid"),
-    ("kMaxGridBlocks (grid striding)", CSRC + "k_spgemm.hip", r"const long long cap = max_grid_blocks\(\);",
+    ("tile loop of the values pass: the product's tile", CSRC + "k_spgemm.hip", r"kSpgemmTile == \(kThreads / kWave\) \* kSpgemmWaveChunk,\n +\"sum_runs derives",
+     ["test_spgemm_grid_stride_at_test_size"], "the shared loop's tile is the launcher's kSpgemmTile"),
+    ("kMaxGridBlocks (grid striding)", CSRC + SHARED, r"const long long cap = max_grid_blocks\(\);",
      ["test_spgemm_grid_stride_at_test_size"], "every kernel of the three entries strides over the work beyond max_grid_blocks() workgroups"),
-    ("long runs leave the lane pass", CSRC + "k_spgemm.hip", r"len\[k\] = l > kCooLongRun \? -l : l;",
+    ("kMaxGridBlocks (grid striding): the product's call", CSRC + "k_spgemm.hip", r"dim3\(grid_for\(nnz_c, kSpgemmTile\)\)",
+     ["test_spgemm_grid_stride_at_test_size"], "the launchers of the three entries take the shared grid"),
+    ("long runs leave the lane pass", CSRC + SHARED, r"len\[k\] = l > kCooLongRun \? -l : l;",
      [GPU, "test_values_follow_new_factors"], "a run of 65 or more products is summed by the wavefront, one run at a time (long_runs: 64, 65, 5 000)"),
-    ("four products per step of a long run", CSRC + "k_spgemm.hip", r"for \(; p \+ 3 \* kWave < end; p \+= 4 \* kWave\)",
+    ("long runs leave the lane pass: the product's call", CSRC + "k_spgemm.hip", r"sum_runs<kSpgemmPerLane>\(nprod, nnz_c, start, SpgemmTerms\{pa, pb, a_value, b_value\}, value\);",
+     [GPU, "test_values_follow_new_factors"], "the values pass is the shared body on the product's terms"),
+    ("four products per step of a long run", CSRC + SHARED, r"for \(; p \+ 3 \* kWave < end; p \+= 4 \* kWave\)",
      [GPU], "long runs: steps of four products per lane, then single ones (65: neither, 5 000: both)"),
+    ("four products per step of a long run: the product's fetch", CSRC + "k_spgemm.hip", r"__device__ __forceinline__ double fetch\(int p\) const \{",
+     [GPU], "what a lane of the long-run path fetches per position: two index loads, two gathers, one rounded product"),
     ("count sizes", CSRC + "k_spgemm.hip", r"rocprim::reduce\(tmp, \*tmp_bytes, count, total, 0LL, static_cast<size_t>\(nnz_a\),",
      [GPU, "test_spgemm_contract"], "the library reduction over 1 ... 800 000 counts, 64-bit: a total of 2.5e9 is a number"),
     ("scan sizes", CSRC + "k_spgemm.hip", r"rocprim::exclusive_scan\(tmp, \*tmp_bytes, count, off, 0LL, static_cast<size_t>\(nnz_a\) \+ 1,",

@@ -26,8 +26,10 @@ SPMM_SIZE_RULES = [
      "rows of more non-zeros are cut into pieces + fix-up (hub rows of 257, 3 000 and 120 001 non-zeros)"),
     ("kSpmmPiece", CSRC + "spmm.hpp", r"constexpr int kSpmmPiece = 256;",
      ["test_spmm_parity", "test_spmm_unrebased_row_range"], "non-zeros per piece of a long row (the fix-up adds up to 470 pieces per row)"),
-    ("kMaxGridBlocks (grid striding)", CSRC + "k_spmm.hip", r"const long long cap = max_grid_blocks\(\);",
+    ("kMaxGridBlocks (grid striding)", CSRC + "structure_passes.hpp", r"const long long cap = max_grid_blocks\(\);",
      ["test_spmm_grid_stride_at_test_size"], "every SpMM kernel strides over the rows beyond max_grid_blocks() workgroups"),
+    ("kMaxGridBlocks (grid striding): SpMM's call", CSRC + "k_spmm.hip", r"dim3\(grid_for\(A\.m, kThreads / TS\)\)",
+     ["test_spmm_grid_stride_at_test_size"], "the SpMM launchers take the shared grid"),
     ("k == 1 route", CSRC + "spmm.cpp", r"if \(k == 1 && \(!row_major \|\| \(ldx == 1 && ldy == 1\)\)\)",
      ["test_spmm_bitwise_invariants", "test_spmm_contract"], "k = 1 with contiguous vectors: the SpMV path under the active strategy"),
     ("64-bit offsets", CSRC + "k_spmm.hip", r"long long ldx, long long ldy",

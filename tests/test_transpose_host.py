@@ -27,8 +27,10 @@ TRANSPOSE_SIZE_RULES = [
      "fixed tiles of the non-zero stream whatever the row lengths; an un-rebased row range starts at the tile that holds rowptr[0]"),
     ("first tile of a view", CSRC + "k_transpose.hip", r"for \(long long tile = lo / kTransTile \+ blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\)",
      ["test_spmv_t_contract", "test_transpose_grid_stride_at_test_size"], "un-rebased sub-range: tiles from rowptr[0] on; blocks stride over the tiles beyond the grid"),
-    ("kMaxGridBlocks (grid striding)", CSRC + "k_transpose.hip", r"const long long cap = max_grid_blocks\(\);",
+    ("kMaxGridBlocks (grid striding)", CSRC + "structure_passes.hpp", r"const long long cap = max_grid_blocks\(\);",
      ["test_transpose_grid_stride_at_test_size"], "every kernel of the three entries strides over the work beyond max_grid_blocks() workgroups"),
+    ("kMaxGridBlocks (grid striding): the transpose's call", CSRC + "k_transpose.hip", r"dim3\(grid_for\(nnz_end, kTransTile\)\)",
+     ["test_transpose_grid_stride_at_test_size"], "the launchers of the three entries take the shared grid"),
     ("sort bits from n", CSRC + "transpose.hpp", r"while \(bits < 31 && \(1LL << bits\) < n\) \+\+bits;",
      ["test_transpose_is_the_host_stable_argsort"], "radix-sort passes follow the column count: n = 37 sorts 6 bits, n = 150 000 sorts 18"),
     ("sort size paths", CSRC + "k_transpose.hip", r"rocprim::radix_sort_pairs\(tmp, \*tmp_bytes, ci, keys_out, rocprim::counting_iterator<int>\(0\), perm,",
