@@ -427,6 +427,71 @@ int spmv_acc_csr_extract(int m, int n, int nnz_a, const int *d_a_rowptr, const i
  * 0.263 / 0.142 / 0.112 / 0.072 ms on the same four maps: within 1 % on the permuted headline map (torch ahead), 6 to 9 % slower elsewhere. */
 int spmv_acc_csr_extract_values(int nnz_c, int nnz_a, const int *d_map, const double *d_a_value, double *d_c_value);
 
+/* ---- multicolour Gauss-Seidel / SOR, 1: the colouring of the pattern (new; analysis) ------------------------------------------------------
+ * replaces: nothing in the reference.  Colours the rows of a square matrix so that no two rows joined by a stored off-diagonal entry share a
+ * colour; the rows of one colour can then be relaxed together, and a Gauss-Seidel sweep is one launch per colour (spmv_acc_csr_gs_sweep).
+ * INPUTS: A is m x m, CSR, int32, rebased (rowptr[0] == 0, rowptr[m] == nnz); its rows STRICTLY ascend and its PATTERN is symmetric (values
+ * are not read).  An unsymmetric matrix: colour the pattern of A + A^T from spmv_acc_csr_transpose and spmv_acc_csr_add -- those colours are
+ * valid for A.
+ * THE RESULT IS UNIQUE, a pure function of the pattern.  Row v has the 64-bit priority (mix32(v) << 32) | v with mix32(x): x ^= x >> 16;
+ * x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (32-bit unsigned).  The rows are taken in descending priority and each gets the
+ * smallest colour >= 0 that no already-coloured off-diagonal neighbour holds.  On the device this is computed in Jones-Plassmann rounds (an
+ * uncoloured row with no uncoloured neighbour of higher priority takes its colour; colours are read from the round before), which gives the
+ * same colours whatever the timing; the number of rounds is a function of the pattern too.
+ * OUTPUTS: d_color[m] = the colour of every row.  *h_ncolors = 1 + the largest colour (0 for m == 0).  d_color_rows[m] = the rows in ascending
+ * (colour, row): a stable sort by colour, which is exactly the perm of a symmetric permutation C[i, j] = A[perm[i], perm[j]] that makes every
+ * colour a contiguous row range.  h_color_ptr, a HOST array of cap_colors + 1 ints: colour c owns the positions [h_color_ptr[c],
+ * h_color_ptr[c + 1]) of d_color_rows.  *h_no_diag = the number of rows that store no diagonal entry (the sweep leaves them untouched).
+ * More than cap_colors colours: SPMV_ACC_ERR_TOO_LARGE, with *h_ncolors, *h_no_diag, d_color and d_color_rows valid and h_color_ptr not
+ * written: call again with a larger array.
+ * CHECKS.  On the host, before the device is touched: negative m or nnz, cap_colors < 1, null pointers where data is needed:
+ * SPMV_ACC_ERR_BAD_ARGUMENT; m or nnz beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  On the device ONE CENSUS, counting (a) rowptr[0] != 0 or
+ * rowptr[m] != nnz, (b) rows whose rowptr extent descends or leaves [0, nnz], (c) columns outside [0, m), (d) positions where a row does not
+ * strictly ascend, (e) off-diagonal entries (i, j) whose mirror (j, i) is not stored: if any count is non-zero, SPMV_ACC_ERR_BAD_ARGUMENT,
+ * nothing was written and the error string holds the counts.  A bad index is never turned into an address.  A group of rounds that colours no
+ * row while some remain (impossible on a pattern that passed the census) ends the call with SPMV_ACC_ERR_HIP instead of another round.
+ * Runs on the calling thread's library stream and has finished when it returns.  No atomic, no kernel that waits on another workgroup: two
+ * calls on the same pattern give the same arrays.  WORKSPACE, one allocation, freed on every path: 20 B per row, 4 B per colour of
+ * h_color_ptr (at most per row), 96 KiB of census counts and the radix sort's scratch.  Inside a stream capture it enqueues nothing and
+ * returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan.  Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST: rounds x one pass over rowptr and colindex (the census one more, with a binary search per off-diagonal entry), one row per lane --
+ * a row of very many entries is walked by a single lane --, one synchronising read per 8 rounds, one radix sort of m keys.  As measured
+ * (MI355X, tools/gs_bench.py, profiles/gs_bench.md): a 9-point FEM-quads matrix of 4.0 M rows and 36.0 M entries 2.38 ms = 32 settled SpMVs
+ * (9 colours, 23 rounds); a 27-point grid of 3.4 M rows and 89.9 M entries 13.9 ms = 73 SpMVs (18 colours, 59 rounds). */
+int spmv_acc_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex,
+                       int *d_color, int *d_color_rows, int cap_colors, int *h_color_ptr,
+                       int *h_ncolors, int *h_no_diag);
+
+/* ---- multicolour Gauss-Seidel / SOR, 2: one sweep (new; the per-step hot path) --------------------------------------------------------------
+ * replaces: nothing in the reference.  One forward (direction 0: colours 0 .. ncolors - 1), backward (1: ncolors - 1 .. 0) or symmetric (2:
+ * forward, then backward) sweep of x towards the solution of A x = b, with the colours of spmv_acc_csr_color: ncolors = *h_ncolors,
+ * h_color_ptr (a host array) and d_color_rows as it left them.  d_color_rows == NULL: the matrix, b and x have been permuted by colour
+ * (C[i, j] = A[perm[i], perm[j]] with perm = d_color_rows) and colour c IS the row range [h_color_ptr[c], h_color_ptr[c + 1]) -- the
+ * coalesced form.  Every row i of a colour is updated in place:  s = the sum of value * x[col] over the row's stored entries with col != i,
+ * g = (b[i] - s) / a_ii,  x[i] = g if omega == 1.0, else x[i] + omega * (g - x[i]).
+ * BIT FOR BIT a pure function of the arrays and of h_color_ptr: every product, the subtraction, the division and the relaxation are rounded on
+ * their own (no fused multiply-add); the diagonal's position and a column outside [0, m) contribute the term +0.0; a row's terms are added by
+ * a group of G lanes, lane l the terms l, l + G, ... in order from its first, the G partial sums as a balanced tree over neighbouring lanes; G
+ * (a power of two, 1 .. 64) is the smallest with 4 G >= the mean row length of the 64 consecutive rows of the colour that one workgroup owns
+ * (spmv_acc_amd/csrc/gs.hpp spells it out, tests/test_gs_host.py host_gs_sweep restates it in numpy).
+ * A row without a stored diagonal is left untouched; a zero diagonal gives what IEEE division gives; a row index outside [0, m) is skipped;
+ * rowptr extents are clamped to [0, nnz]: crafted arrays cannot make it read or write outside the caller's arrays.  THE ENTRY CANNOT CHECK
+ * THAT THE COLOURS ARE VALID FOR THE PATTERN: with two joined rows in one colour the launch races and the result is not defined (nothing
+ * faults).
+ * One launch per non-empty colour on the calling thread's library stream, in order: asynchronous, no allocation, no synchronisation, no
+ * copy, no plan; may be captured into a hipGraph (one stream, no parallel branches).  CHECKS, on the host, nothing launched: null pointers
+ * where data is needed, negative sizes, direction outside 0 .. 2, h_color_ptr not ascending from 0 to m, d_b overlapping d_x:
+ * SPMV_ACC_ERR_BAD_ARGUMENT; a size beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  Returns 0 or an spmv_acc_error code.
+ * COST: per direction the bytes of one SpMV (12 B per non-zero, rowptr, b, x) in ncolors launches.  As measured (MI355X, tools/gs_bench.py,
+ * profiles/gs_bench.md; one symmetric sweep beside two settled SpMVs of the engine on the same matrix in the same process): the FEM-quads
+ * matrix above, 18 launches, 0.454 ms colour-permuted = 3.0 x two SpMVs (0.0753 ms each) and 0.813 ms through d_color_rows = 5.4 x; the
+ * 27-point grid, 36 launches, 1.146 ms = 3.0 x (SpMV 0.190 ms) and 1.380 ms = 3.6 x.  Replayed from a graph: the same times.  A launch
+ * with nothing to move costs 4.4 us replayed, so the launch count is a quarter to a fifth of the gap; the rest is the kernel (supposed, not
+ * checked: x lines are fetched once per colour, and short rows fill their lane group's step only partly). */
+int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
+                          int ncolors, const int *h_color_ptr, const int *d_color_rows,
+                          double omega, int direction, const double *d_b, double *d_x);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

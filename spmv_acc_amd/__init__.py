@@ -45,6 +45,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_spgemm_products", "spmv_acc_csr_spgemm", "spmv_acc_csr_spgemm_values",
     "spmv_acc_csr_add", "spmv_acc_csr_add_values",
     "spmv_acc_csr_extract", "spmv_acc_csr_extract_values",
+    "spmv_acc_csr_color", "spmv_acc_csr_gs_sweep",
 )
 
 _lib = None
@@ -165,6 +166,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_extract.restype = ci
     lib.spmv_acc_csr_extract_values.argtypes = [ci, ci, vp, vp, vp]
     lib.spmv_acc_csr_extract_values.restype = ci
+    lib.spmv_acc_csr_color.argtypes = [ci, ci, vp, vp, vp, vp, ci, _c_int_p, _c_int_p, _c_int_p]
+    lib.spmv_acc_csr_color.restype = ci
+    lib.spmv_acc_csr_gs_sweep.argtypes = [ci, ci, vp, vp, vp, ci, _c_int_p, vp, cd, ci, vp, vp]
+    lib.spmv_acc_csr_gs_sweep.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -705,6 +710,92 @@ def csr_permute(m: int, rowptr, colindex, value, perm, want_map: bool = False):
             raise SpmvAccError(f"perm: values in [{low}, {high}], a permutation of the rows holds [0, {m})")
         inverse[perm.long()] = torch.arange(m, dtype=torch.int32, device=perm.device)
     return csr_extract(m, m, rowptr, colindex, value, rows=perm, colmap=inverse, nc=m, want_map=want_map)
+
+
+_GS_DIRECTIONS = {"forward": 0, "backward": 1, "symmetric": 2}
+_GS_FIRST_CAP = 1024  # colours csr_color makes room for before it asks the entry how many there are
+
+
+def csr_color(m: int, rowptr, colindex):
+    """The multicolour ordering of a square m x m CSR with strictly ascending rows and a symmetric pattern (spmv_acc_csr_color): returns
+    (color, color_rows, color_ptr, no_diag).  color[v]: the colour of row v, the greedy colouring in descending priority (mix32(v) << 32) | v
+    -- unique, a pure function of the pattern.  color_rows: the rows in ascending (colour, row), int32 on the GPU.  color_ptr: a HOST list,
+    colour c owns color_rows[color_ptr[c]:color_ptr[c + 1]]; len(color_ptr) - 1 colours.  no_diag: rows without a stored diagonal (a sweep
+    leaves them untouched).  len(colindex) must be rowptr[m].  An unsymmetric matrix: colour the pattern of A + A^T (csr_transpose, csr_add).
+    Synchronises; not capturable.
+
+    Sweeps on the original matrix:   csr_gs_sweep(m, rowptr, colindex, value, color_ptr, color_rows, b, x)
+    The colour-permuted, coalesced form -- every colour a contiguous row range:
+        p_rowptr, p_colindex, p_value = csr_permute(m, rowptr, colindex, value, perm=color_rows)
+        pb, px = b[color_rows.long()], x[color_rows.long()]
+        csr_gs_sweep(m, p_rowptr, p_colindex, p_value, color_ptr, None, pb, px)        # color_rows=None
+        x[color_rows.long()] = px"""
+    import torch
+
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(rowptr=rowptr, colindex=colindex)
+    nnz = int(colindex.numel())
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0))
+    dev = rowptr.device
+    color = torch.empty(m, dtype=torch.int32, device=dev)
+    color_rows = torch.empty(m, dtype=torch.int32, device=dev)
+    cap = _GS_FIRST_CAP
+    for attempt in range(2):  # (the second with the count the first returned)
+        h_ptr = (ctypes.c_int * (cap + 1))()
+        h_ncolors, h_no_diag = ctypes.c_int(0), ctypes.c_int(0)
+        rc = lib.spmv_acc_csr_color(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(color) if m else 0, _ptr(color_rows) if m else 0,
+                                    cap, h_ptr, ctypes.byref(h_ncolors), ctypes.byref(h_no_diag))
+        if rc == 4 and attempt == 0 and h_ncolors.value > cap:  # SPMV_ACC_ERR_TOO_LARGE: more colours than the first array holds
+            lib.spmv_acc_clear_error()
+            cap = int(h_ncolors.value)
+            continue
+        break
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_color failed ({rc})")
+    return color, color_rows, [int(h_ptr[c]) for c in range(h_ncolors.value + 1)], int(h_no_diag.value)
+
+
+def csr_gs_sweep(m: int, rowptr, colindex, value, color_ptr, color_rows, b, x, omega: float = 1.0, direction="symmetric", sweeps: int = 1) -> None:
+    """`sweeps` multicolour Gauss-Seidel (omega = 1) / SOR sweeps of x towards A x = b, in place (spmv_acc_csr_gs_sweep, async on torch's
+    current stream, capturable): direction "forward", "backward" or "symmetric" (forward, then backward); color_ptr and color_rows from
+    csr_color on the same pattern.  color_rows=None: the matrix, b and x are permuted by colour (csr_color's docstring) and colour c is the row
+    range color_ptr[c]:color_ptr[c + 1].  One launch per non-empty colour and direction.  Bit for bit a pure function of the arrays and of
+    color_ptr.  A row without a stored diagonal is left untouched.  b must not overlap x."""
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    if direction not in _GS_DIRECTIONS:
+        raise SpmvAccError(f"direction {direction!r}: one of {tuple(_GS_DIRECTIONS)}")
+    if int(sweeps) < 0:
+        raise SpmvAccError(f"negative sweeps ({sweeps})")
+    _require_tensors(rowptr=rowptr, colindex=colindex, value=value, b=b, x=x)
+    nnz = int(colindex.numel())
+    if int(value.numel()) > nnz:  # (fewer: the "elements" check below)
+        raise SpmvAccError(f"colindex holds {nnz} elements, value must hold as many")
+    named = dict(rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0), value=(value, "f64", nnz), b=(b, "f64", m), x=(x, "f64", m))
+    if color_rows is not None:
+        _require_tensors(color_rows=color_rows)
+        if int(color_rows.numel()) != m:
+            raise SpmvAccError(f"color_rows holds {int(color_rows.numel())} elements, the {m} rows in colour order must be as many")
+        named["color_rows"] = (color_rows, "i32", m)
+    try:
+        ptr = [int(p) for p in color_ptr]
+    except TypeError:
+        raise SpmvAccError("color_ptr: a host list of ints (csr_color returns it)") from None
+    if not ptr or ptr[0] != 0 or ptr[-1] != m or any(hi < lo for lo, hi in zip(ptr, ptr[1:])):
+        raise SpmvAccError(f"color_ptr must ascend from 0 to m = {m}")
+    _require(lib, **named)
+    h_ptr = (ctypes.c_int * len(ptr))(*ptr)
+    for _ in range(int(sweeps)):
+        rc = lib.spmv_acc_csr_gs_sweep(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(value) if nnz else 0, len(ptr) - 1, h_ptr,
+                                       _ptr(color_rows) if color_rows is not None and m else 0, float(omega), _GS_DIRECTIONS[direction],
+                                       _ptr(b) if m else 0, _ptr(x) if m else 0)
+        if rc != 0:
+            _check(lib)
+            raise SpmvAccError(f"csr_gs_sweep failed ({rc})")
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

@@ -18,6 +18,7 @@
 #include "spgemm.hpp"
 #include "csr_add.hpp"
 #include "extract.hpp"
+#include "gs.hpp"
 
 #include <string>
 #include <cstdint>
@@ -262,6 +263,16 @@ int spmv_acc_csr_extract(int m, int n, int nnz_a, const int *d_a_rowptr, const i
 
 int spmv_acc_csr_extract_values(int nnz_c, int nnz_a, const int *d_map, const double *d_a_value, double *d_c_value) {
   return run_csr_extract_values(nnz_c, nnz_a, d_map, d_a_value, d_c_value);
+}
+
+int spmv_acc_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, int *d_color, int *d_color_rows, int cap_colors, int *h_color_ptr,
+                       int *h_ncolors, int *h_no_diag) {
+  return run_csr_color(m, nnz, d_rowptr, d_colindex, d_color, d_color_rows, cap_colors, h_color_ptr, h_ncolors, h_no_diag);
+}
+
+int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, int ncolors, const int *h_color_ptr,
+                          const int *d_color_rows, double omega, int direction, const double *d_b, double *d_x) {
+  return run_csr_gs_sweep(m, nnz, d_rowptr, d_colindex, d_value, ncolors, h_color_ptr, d_color_rows, omega, direction, d_b, d_x);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
