@@ -492,6 +492,68 @@ int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_coli
                           int ncolors, const int *h_color_ptr, const int *d_color_rows,
                           double omega, int direction, const double *d_b, double *d_x);
 
+/* ---- aggregation coarsening, 1: distance-2 independent roots and their aggregates (new; analysis) ------------------------------------------
+ * replaces: nothing in the reference.  The coarsening step of an aggregation algebraic-multigrid setup on the device: it groups the rows of a
+ * square matrix into aggregates and returns them as the CSR structures of the tentative prolongator P (m x naggs, one entry per row) and of
+ * its transpose R, so that the Galerkin product R (A P) is two spmv_acc_csr_spgemm calls on the returned arrays, without a transpose.
+ * INPUTS: the pattern of the STRENGTH GRAPH, m x m, CSR, int32, rebased (rowptr[0] == 0, rowptr[m] == nnz); its rows STRICTLY ascend and it
+ * is symmetric (values are not read, a stored diagonal is not required).  For the matrix itself pass its own pattern.  A filter that drops
+ * weak entries by a value threshold is out of scope: filter first (spmv_acc_csr_extract keeps a sub-pattern), and for an unsymmetric matrix
+ * aggregate the pattern of A + A^T (spmv_acc_csr_transpose, spmv_acc_csr_add).
+ * THE RESULT IS UNIQUE, a pure function of the pattern.  Row v has the priority of spmv_acc_csr_color, (mix32(v) << 32) | v; distances are
+ * counted over off-diagonal entries.  ROOTS: the rows are taken in descending priority and a row becomes a root if no root already chosen lies
+ * within distance 2 of it -- the lexicographically first distance-2 maximal independent set; an isolated row is a root.  The roots are
+ * numbered 0 .. naggs - 1 in ascending row order.  A: a non-root with a root neighbour joins that root's aggregate (there is at most one).
+ * B: every remaining row joins the smallest aggregate id among its neighbours that were assigned as a root or in A.  On the device the roots
+ * are found in rounds (a row is decided from the largest key within distance 2 of it, two passes over the pattern per round; 8 to 12 rounds on
+ * a mesh), which gives the same sets whatever the timing.
+ * OUTPUTS: d_agg[m] = the aggregate of every row.  d_agg_rows[m] = the rows in ascending (aggregate, row), a stable sort.  d_agg_ptr[m + 1]:
+ * d_agg_ptr[a] = the first position of aggregate a in d_agg_rows for a <= naggs, and m for naggs < a <= m.  *h_naggs.  (d_agg_ptr[0 ..
+ * naggs], d_agg_rows) is the structure of R with ascending rows; (0, 1, .. m, d_agg) is that of P.
+ * CHECKS.  On the host, before the device is touched: negative m or nnz, null pointers where data is needed: SPMV_ACC_ERR_BAD_ARGUMENT; m or
+ * nnz beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  On the device the colouring's ONE CENSUS, counting (a) rowptr[0] != 0 or rowptr[m] !=
+ * nnz, (b) rows whose rowptr extent descends or leaves [0, nnz], (c) columns outside [0, m), (d) positions where a row does not strictly
+ * ascend, (e) off-diagonal entries (i, j) whose mirror (j, i) is not stored: if any count is non-zero, SPMV_ACC_ERR_BAD_ARGUMENT, nothing was
+ * written and the error string holds the counts.  Rows are read clamped and a bad index is never turned into an address.  A group of rounds that
+ * decides no row while some remain, or a row without an aggregate after B (both impossible on a pattern that passed the census), ends the call
+ * with SPMV_ACC_ERR_HIP instead of another round.  CANNOT CHECK: that the pattern is the strength graph the caller meant.
+ * Runs on the calling thread's library stream and has finished when it returns.  No atomic, no kernel that waits on another workgroup: two
+ * calls on the same pattern give the same arrays.  WORKSPACE, one allocation, freed on every path: 28 B per row, 96 KiB of counts and the
+ * scratch of the scan and the radix sort.  Inside a stream capture it enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and
+ * touches no plan.  Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST: the census, then per round two passes over rowptr and colindex with one 8-byte gather per entry (the second pass only for the rows
+ * still undecided), one row per lane, one synchronising read per 4 rounds; one scan, two assignment passes, one radix sort of m keys.
+ * As measured (MI355X, tools/agg_bench.py, profiles/agg_bench.md): a 9-point FEM-quads matrix of 4.0 M rows and 36.0 M entries 3.00 ms = 40
+ * settled SpMVs = 1.28 x spmv_acc_csr_color on the same matrix (13 rounds, 302 683 aggregates of 13 rows); a 27-point grid of 3.4 M rows and
+ * 89.9 M entries 9.37 ms = 51 SpMVs = 0.68 x the colouring (16 rounds, 71 946 aggregates of 47 rows).  A lane group per row was measured
+ * and not kept: four lanes gain 3 % on the grid and lose 38 % on the mesh. */
+int spmv_acc_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_colindex,
+                           int *d_agg, int *d_agg_rows, int *d_agg_ptr, int *h_naggs);
+
+/* ---- aggregation coarsening, 2: the tentative prolongator's values (new; the per-step values pass) ------------------------------------------
+ * replaces: nothing in the reference.  The one-vector QR of smoothed aggregation on the aggregates of spmv_acc_csr_aggregate: d_b is the fine
+ * near-nullspace vector (NULL: all ones), and with s[a] = the sum of d_b[i]^2 over the rows i of aggregate a,
+ *   d_bc[a] = sqrt(s[a]) (naggs doubles: the coarse near-nullspace vector),  d_p_value[i] = d_b[i] / d_bc[d_agg[i]] (m doubles: the values of
+ *   P in its CSR order),  d_r_value[p] = d_p_value[d_agg_rows[p]] (m doubles, or NULL: the values of R = P^T in its CSR order).
+ * The columns of P are orthonormal: P^T P = I to rounding.  With d_b == NULL every value is 1 / sqrt(the aggregate's size).
+ * BIT FOR BIT a pure function of the arrays: every square is rounded on its own (no fused multiply-add) and an aggregate's squares are added
+ * in the summation order of spmv_acc_coo_to_csr_values over the run [d_agg_ptr[a], d_agg_ptr[a + 1]) of d_agg_rows; the square root and the
+ * division are correctly rounded; a zero norm gives +0.0 in P, not a division by zero.
+ * The maps are the caller's arrays: runs are clamped to [0, m]; a d_agg[i] outside [0, naggs) gives d_p_value[i] = +0.0; a d_agg_rows[p]
+ * outside [0, m) contributes +0.0 to its norm and gives d_r_value[p] = +0.0: crafted arrays cannot make it read or write outside the caller's
+ * arrays.  CANNOT CHECK that d_agg, d_agg_ptr and d_agg_rows describe the same aggregates: pass them as spmv_acc_csr_aggregate left them
+ * (d_agg_ptr must hold naggs + 1 ints).
+ * Two launches on the calling thread's library stream, the norms and then the values: asynchronous, no allocation, no synchronisation, no
+ * copy, no plan; may be captured into a hipGraph.  CHECKS, on the host, nothing launched: negative sizes, null pointers where data is needed,
+ * d_b or d_bc overlapping an output, outputs overlapping each other: SPMV_ACC_ERR_BAD_ARGUMENT; a size beyond INT_MAX - 2^16:
+ * SPMV_ACC_ERR_TOO_LARGE.  Returns 0 or an spmv_acc_error code.
+ * COST: at least 36 B per row with d_r_value and d_b (d_agg, d_agg_rows twice, b, two outputs) and 20 B per aggregate; one lane adds an
+ * aggregate's squares one after the other.  As measured (the same tool, file and matrices): 0.105 ms on the FEM-quads aggregates = 4.8 x a
+ * device copy of those bytes, 0.125 ms on the grid's = 6.9 x; replayed from a graph: the same times.  Supposed, not checked: the norms are
+ * bound by the latency of their dependent gathers, R's values by three dependent gathers per entry. */
+int spmv_acc_csr_tentative_values(int m, int naggs, const int *d_agg, const int *d_agg_ptr, const int *d_agg_rows,
+                                  const double *d_b, double *d_p_value, double *d_r_value, double *d_bc);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

@@ -46,6 +46,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_add", "spmv_acc_csr_add_values",
     "spmv_acc_csr_extract", "spmv_acc_csr_extract_values",
     "spmv_acc_csr_color", "spmv_acc_csr_gs_sweep",
+    "spmv_acc_csr_aggregate", "spmv_acc_csr_tentative_values",
 )
 
 _lib = None
@@ -170,6 +171,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_color.restype = ci
     lib.spmv_acc_csr_gs_sweep.argtypes = [ci, ci, vp, vp, vp, ci, _c_int_p, vp, cd, ci, vp, vp]
     lib.spmv_acc_csr_gs_sweep.restype = ci
+    lib.spmv_acc_csr_aggregate.argtypes = [ci, ci, vp, vp, vp, vp, vp, _c_int_p]
+    lib.spmv_acc_csr_aggregate.restype = ci
+    lib.spmv_acc_csr_tentative_values.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.spmv_acc_csr_tentative_values.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -796,6 +801,95 @@ def csr_gs_sweep(m: int, rowptr, colindex, value, color_ptr, color_rows, b, x, o
         if rc != 0:
             _check(lib)
             raise SpmvAccError(f"csr_gs_sweep failed ({rc})")
+
+
+def csr_aggregate(m: int, rowptr, colindex):
+    """Aggregation coarsening of a square m x m CSR pattern with strictly ascending rows and a symmetric pattern -- the strength graph; for
+    the matrix itself its own pattern -- (spmv_acc_csr_aggregate): returns (agg, agg_ptr, agg_rows, naggs).  The roots are the
+    lexicographically first distance-2 maximal independent set in descending priority (mix32(v) << 32) | v, numbered in ascending row order;
+    a row next to a root joins it, every other row joins the smallest aggregate among its assigned neighbours -- unique, a pure function of the
+    pattern.  agg[v]: the aggregate of row v.  agg_rows: the rows in ascending (aggregate, row).  agg_ptr: naggs + 1 entries, aggregate a
+    owns agg_rows[agg_ptr[a]:agg_ptr[a + 1]].  All int32 on the GPU; naggs a host int.  len(colindex) must be rowptr[m].  Synchronises; not
+    capturable.
+
+    The Galerkin product A_c = P^T A P on the device, P from csr_tentative:
+        agg, agg_ptr, agg_rows, naggs = csr_aggregate(m, rowptr, colindex)
+        P, R, bc = csr_tentative(m, agg, agg_ptr, agg_rows, b)                        # P = (p_rowptr, p_colindex, p_value), R = P^T
+        AP = csr_spgemm(m, m, naggs, rowptr, colindex, value, *P)
+        c_rowptr, c_colindex, c_value = csr_spgemm(naggs, m, naggs, *R, *AP)          # bc: the near-nullspace vector of the next level"""
+    import torch
+
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(rowptr=rowptr, colindex=colindex)
+    nnz = int(colindex.numel())
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0))
+    dev = rowptr.device
+    agg = torch.empty(m, dtype=torch.int32, device=dev)
+    agg_rows = torch.empty(m, dtype=torch.int32, device=dev)
+    agg_ptr = torch.zeros(m + 1, dtype=torch.int32, device=dev)  # (no rows: agg_ptr = [0], the entry touches nothing)
+    h_naggs = ctypes.c_int(0)
+    rc = lib.spmv_acc_csr_aggregate(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(agg) if m else 0, _ptr(agg_rows) if m else 0,
+                                    _ptr(agg_ptr) if m else 0, ctypes.byref(h_naggs))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_aggregate failed ({rc})")
+    naggs = int(h_naggs.value)
+    return agg, agg_ptr[:naggs + 1].clone(), agg_rows, naggs
+
+
+def csr_tentative_values(m: int, agg, agg_ptr, agg_rows, b, p_value, r_value, bc) -> None:
+    """The values of the tentative prolongator on the aggregates of csr_aggregate, in place (spmv_acc_csr_tentative_values, async on torch's
+    current stream, capturable): bc[a] = the 2-norm of b over aggregate a, p_value[i] = b[i] / bc[agg[i]], r_value[p] = p_value[agg_rows[p]].
+    b=None: all ones.  r_value=None: not wanted.  naggs = len(agg_ptr) - 1 = len(bc).  Bit for bit a pure function of the arrays; a zero norm
+    gives +0.0, not a division by zero.  b and bc must not overlap an output."""
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(agg=agg, agg_ptr=agg_ptr, agg_rows=agg_rows, p_value=p_value, bc=bc)
+    naggs = int(agg_ptr.numel()) - 1
+    if naggs < 0:
+        raise SpmvAccError("agg_ptr: 0 elements, the pointer of no aggregate still holds one")
+    for name, t, count, what in (("agg", agg, m, f"the aggregates of the {m} rows"), ("agg_rows", agg_rows, m, f"the {m} rows in aggregate order"),
+                                 ("bc", bc, naggs, f"the norms of the {naggs} aggregates of agg_ptr")):
+        if int(t.numel()) != count:
+            raise SpmvAccError(f"{name} holds {int(t.numel())} elements, {what} must be as many")
+    named = dict(agg=(agg, "i32", m), agg_ptr=(agg_ptr, "i32", naggs + 1), agg_rows=(agg_rows, "i32", m), p_value=(p_value, "f64", m),
+                 bc=(bc, "f64", naggs))
+    if b is not None:
+        _require_tensors(b=b)
+        named["b"] = (b, "f64", m)
+    if r_value is not None:
+        _require_tensors(r_value=r_value)
+        named["r_value"] = (r_value, "f64", m)
+    _require(lib, **named)
+    rc = lib.spmv_acc_csr_tentative_values(m, naggs, _ptr(agg) if m else 0, _ptr(agg_ptr), _ptr(agg_rows) if m else 0,
+                                           _ptr(b) if b is not None and m else 0, _ptr(p_value) if m else 0,
+                                           _ptr(r_value) if r_value is not None and m else 0, _ptr(bc) if naggs else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_tentative_values failed ({rc})")
+
+
+def csr_tentative(m: int, agg, agg_ptr, agg_rows, b=None):
+    """The tentative prolongator of smoothed aggregation and its transpose as CSR matrices, from csr_aggregate's arrays: returns
+    ((p_rowptr, p_colindex, p_value), (r_rowptr, r_colindex, r_value), bc).  P is m x naggs with one entry per row: p_rowptr = arange(m + 1),
+    p_colindex IS agg; R = P^T is naggs x m with ascending rows: r_rowptr IS agg_ptr, r_colindex IS agg_rows (no copies).  The values and bc:
+    csr_tentative_values, which also refreshes them in place for a new b."""
+    import torch
+
+    _require_tensors(agg=agg, agg_ptr=agg_ptr)
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    dev = agg.device
+    naggs = max(int(agg_ptr.numel()) - 1, 0)
+    p_value = torch.empty(m, dtype=torch.float64, device=dev)
+    r_value = torch.empty(m, dtype=torch.float64, device=dev)
+    bc = torch.empty(naggs, dtype=torch.float64, device=dev)
+    csr_tentative_values(m, agg, agg_ptr, agg_rows, b, p_value, r_value, bc)
+    p_rowptr = torch.arange(m + 1, dtype=torch.int32, device=dev)
+    return (p_rowptr, agg, p_value), (agg_ptr, agg_rows, r_value), bc
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

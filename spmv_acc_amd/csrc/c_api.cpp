@@ -19,6 +19,7 @@
 #include "csr_add.hpp"
 #include "extract.hpp"
 #include "gs.hpp"
+#include "agg.hpp"
 
 #include <string>
 #include <cstdint>
@@ -273,6 +274,15 @@ int spmv_acc_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colinde
 int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, int ncolors, const int *h_color_ptr,
                           const int *d_color_rows, double omega, int direction, const double *d_b, double *d_x) {
   return run_csr_gs_sweep(m, nnz, d_rowptr, d_colindex, d_value, ncolors, h_color_ptr, d_color_rows, omega, direction, d_b, d_x);
+}
+
+int spmv_acc_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_colindex, int *d_agg, int *d_agg_rows, int *d_agg_ptr, int *h_naggs) {
+  return run_csr_aggregate(m, nnz, d_rowptr, d_colindex, d_agg, d_agg_rows, d_agg_ptr, h_naggs);
+}
+
+int spmv_acc_csr_tentative_values(int m, int naggs, const int *d_agg, const int *d_agg_ptr, const int *d_agg_rows, const double *d_b,
+                                  double *d_p_value, double *d_r_value, double *d_bc) {
+  return run_csr_tentative_values(m, naggs, d_agg, d_agg_ptr, d_agg_rows, d_b, d_p_value, d_r_value, d_bc);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
