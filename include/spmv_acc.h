@@ -814,7 +814,14 @@ enum spmv_acc_error {
  * (round 5: like the DMA write of the reference's hipMemcpy reset, csr_spmv.hpp:68, it parks nothing in the L2s; env SPMV_ACC_RESET_NT=0: the
  * default-policy copy of rounds 1-4, SPMV_ACC_RESET_MEMCPY=1: hipMemcpyAsync device -> device).
  * ms_out receives iters per-launch durations in milliseconds.  Returns 0 or an error code.  What is timed is a SETTLED plan: the helpers
- * first finish whatever per-matrix timings the first-call budget left open (spmv_acc_prepare_beta: at least one untimed SpMV into a scratch y). */
+ * first finish whatever per-matrix timings the first-call budget left open (spmv_acc_prepare_beta: at least one untimed SpMV into a scratch y).
+ * d_y0 == NULL: no reset, the launches accumulate into y (as the launches of spmv_acc_time_spmv_total / _region do).  The reset writes dy[0 .. m) and
+ * nothing else, whatever the alignment of dy and d_y0 (both on a 16-byte line: the copy kernel, with a one-workgroup tail for the last double of an
+ * odd m; else hipMemcpyAsync).
+ * REFUSALS, the same for every spmv_acc_time_* entry below: iters <= 0 or a NULL result pointer (ms_out / total_ms_out / kernel_ms_out):
+ * SPMV_ACC_ERR_BAD_ARGUMENT; a strategy id no strategy has (e.g. the -1 of spmv_acc_parse_strategy): SPMV_ACC_ERR_UNKNOWN_STRATEGY.  Either way
+ * nothing is launched and nothing is written, neither to y nor to a result.  m == 0: returns 0 and launches no SpMV; y is not touched and the
+ * times are those of the empty protocol (finite, >= 0). */
 int spmv_acc_time_spmv(int strategy, int iters, double alpha, double beta, int m, int n, int nnz,
                        const int *h_rowptr, const int *d_rowptr, const int *d_colindex, const double *d_value,
                        const double *dx, double *dy, const double *d_y0, float *ms_out);
@@ -832,7 +839,9 @@ int spmv_acc_time_spmv_events(int strategy, int iters, double alpha, double beta
  * start event, flush_bytes of scratch traffic under the default cache policy (the copy kernel: second half of d_flush overwritten with the first)
  * displace what the previous launch left in the L2s and the 256 MB Infinity Cache.  The reference's protocol (benchmark/csr_spmv.hpp:49-74) repeats
  * one SpMV on one matrix, so its launches start in whatever the previous one left; this entry says how much of a figure that is.  d_flush: device
- * memory, 16-byte aligned, flush_bytes >= 2 x the Infinity Cache (the bench passes 1 GiB).  No reference counterpart. */
+ * memory, 16-byte aligned, flush_bytes >= 2 x the Infinity Cache (the bench passes 1 GiB).  With half = flush_bytes / 2 / 16 * 16 the copy writes
+ * bytes [half, 2 * half) of d_flush from bytes [0, half) and touches no other byte.  d_flush == NULL, flush_bytes < 32 or a d_flush off a 16-byte
+ * line: SPMV_ACC_ERR_BAD_ARGUMENT ("... 16-byte aligned ..."), nothing is launched or written.  No reference counterpart. */
 int spmv_acc_time_spmv_cold(int strategy, int iters, double alpha, double beta, int m, int n, int nnz,
                             const int *h_rowptr, const int *d_rowptr, const int *d_colindex, const double *d_value,
                             const double *dx, double *dy, const double *d_y0, void *d_flush, long long flush_bytes, float *ms_out);
@@ -852,12 +861,17 @@ int spmv_acc_time_spmv_kernels(int strategy, int iters, double alpha, double bet
                                const double *dx, double *dy, const double *d_y0, float *event_ms_out, float *kernel_ms_out, int *launches_out);
 /* The same region and NOTHING else (round 5): no plan work -- the caller settles the plan first (spmv_acc_prepare_beta) --, no allocation, the
  * event pair is made once per host thread.  A wall clock around this call, between two device synchronisations, reads the K launches' own time
- * (bench.py's `value` / `ms_per_step`: median over repeated regions, the reference's median rule, benchmark/utils/benchmark_time.cpp:23-43). */
+ * (bench.py's `value` / `ms_per_step`: median over repeated regions, the reference's median rule, benchmark/utils/benchmark_time.cpp:23-43).
+ * A region that did plan work after all (no spmv_acc_prepare_beta in the call's beta class since the plan was made or released) returns
+ * SPMV_ACC_ERR_BAD_ARGUMENT ("... the plan was not settled ..."): y holds the `iters` launches' result and *total_ms_out is written, but it
+ * holds the plan work too. */
 int spmv_acc_time_spmv_region(int strategy, int iters, double alpha, double beta, int m, int n, int nnz,
                               const int *h_rowptr, const int *d_rowptr, const int *d_colindex, const double *d_value,
                               const double *dx, double *dy, float *total_ms_out);
 /* Streaming-copy ceiling (GB/s, read + write bytes) with the kernels' 16-B non-temporal access shape;
- * replaces: the WITH_MEM_BANDWIDTH macros of src/acc/common/mem_bandwidth.hpp:13-38 as the yardstick. */
+ * replaces: the WITH_MEM_BANDWIDTH macros of src/acc/common/mem_bandwidth.hpp:13-38 as the yardstick.
+ * Copies bytes / 16 * 16 bytes from d_src to d_dst (both 16-byte aligned, not overlapping) and writes nothing beyond; best of `reps` after one
+ * warm-up.  A NULL pointer, bytes < 16 or reps <= 0: returns -1.0 and launches nothing (also -1.0 when a HIP call fails). */
 double spmv_acc_copy_ceiling_gbs(void *d_dst, const void *d_src, long long bytes, int reps);
 
 /* ---- switches (new) -------------------------------------------------------------------------------------------------

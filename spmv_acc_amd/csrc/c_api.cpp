@@ -757,6 +757,12 @@ int spmv_acc_time_spmv_region(int strategy, int iters, double alpha, double beta
     set_error(kErrBadArgument, "spmv_acc_time_spmv_region: bad argument");
     return kErrBadArgument;
   }
+  // (the other timing entries meet an unknown id in spmv_acc_prepare_beta, before they write anything; this one prepares nothing, and every launch of
+  // the region would refuse on its own -- behind an event pair whose empty interval used to be written as the region's time)
+  if (m > 0 && (strategy < 0 || strategy >= kStrategyCount)) {
+    set_error(kErrUnknownStrategy, "unknown strategy id");
+    return kErrUnknownStrategy;
+  }
   thread_local hipEvent_t ev[2] = {nullptr, nullptr};
   thread_local int ev_device = -1;
   int dev = -1;
