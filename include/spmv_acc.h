@@ -498,7 +498,8 @@ int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_coli
  * its transpose R, so that the Galerkin product R (A P) is two spmv_acc_csr_spgemm calls on the returned arrays, without a transpose.
  * INPUTS: the pattern of the STRENGTH GRAPH, m x m, CSR, int32, rebased (rowptr[0] == 0, rowptr[m] == nnz); its rows STRICTLY ascend and it
  * is symmetric (values are not read, a stored diagonal is not required).  For the matrix itself pass its own pattern.  A filter that drops
- * weak entries by a value threshold is out of scope: filter first (spmv_acc_csr_extract keeps a sub-pattern), and for an unsymmetric matrix
+ * weak entries by a value threshold is out of scope of this entry: spmv_acc_csr_strength does it -- filter first (its kept pattern is what this
+ * entry takes; spmv_acc_csr_extract keeps a sub-pattern), and for an unsymmetric matrix
  * aggregate the pattern of A + A^T (spmv_acc_csr_transpose, spmv_acc_csr_add).
  * THE RESULT IS UNIQUE, a pure function of the pattern.  Row v has the priority of spmv_acc_csr_color, (mix32(v) << 32) | v; distances are
  * counted over off-diagonal entries.  ROOTS: the rows are taken in descending priority and a row becomes a root if no root already chosen lies
@@ -553,6 +554,76 @@ int spmv_acc_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_col
  * bound by the latency of their dependent gathers, R's values by three dependent gathers per entry. */
 int spmv_acc_csr_tentative_values(int m, int naggs, const int *d_agg, const int *d_agg_ptr, const int *d_agg_rows,
                                   const double *d_b, double *d_p_value, double *d_r_value, double *d_bc);
+
+/* ---- strength of connection, 1: the kept pattern of a value threshold and the partition of A's positions (new; analysis) ---------------------
+ * replaces: nothing in the reference.  The filter of an aggregation algebraic-multigrid setup on the device: it drops the WEAK couplings of a
+ * square matrix by the classical symmetric criterion and returns the kept pattern S -- the strength graph spmv_acc_csr_aggregate takes -- and
+ * a stable partition of A's positions into kept and dropped, from which spmv_acc_csr_strength_values forms the filtered matrix and the
+ * prolongator smoother per step.
+ * INPUTS: A, m x m, CSR, int32 / fp64, rebased (rowptr[0] == 0, rowptr[m] == nnz); its rows STRICTLY ascend and its PATTERN is symmetric (the
+ * contract of spmv_acc_csr_color); the values may be unsymmetric.  theta: finite, >= 0 (0.25 is customary; 0 keeps every finite entry).
+ * THE RESULT IS UNIQUE TO THE BIT, a pure function of the arrays and theta.  sd[i] = sqrt(|a_ii|), correctly rounded, +0.0 for a row without a
+ * stored diagonal.  For an off-diagonal entry (i, j): rhs = fl(fl(sd[i] * sd[j]) * theta) -- the same bits at both ends of the edge, no square
+ * root per entry, and no a_ii * a_jj that could overflow --; the entry is KEPT iff |a_ij| >= rhs or |a_ji| >= rhs, a_ji the value at the
+ * mirror position (a binary search of row j).  IEEE comparisons: a NaN on either side is false.  A stored diagonal entry is always kept.  The
+ * kept pattern is therefore symmetric whatever the values; a row whose diagonal is zero or missing keeps its finite couplings.
+ * OUTPUTS: S = the kept entries in A's order (a stable compaction: rows still strictly ascend, nothing is sorted): d_s_rowptr[m + 1],
+ * d_s_colindex (nnz ints of room, written in [0, nnz_s)).  d_map[nnz]: a stable partition of A's positions, d_map[0 .. nnz_s) the kept
+ * positions ascending (d_map[k] = the position in A of S's entry k), d_map[nnz_s .. nnz) the dropped positions ascending.  d_drop_ptr[m + 1]:
+ * d_drop_ptr[i] = the first place of row i's dropped positions in d_map, in [nnz_s, nnz]; d_drop_ptr[m] = nnz.  *h_nnz_s, and *h_no_diag =
+ * the number of rows without a stored diagonal (not an error); both are written last.
+ * CHECKS.  On the host, before the device is touched: negative m or nnz, null pointers where data is needed, a theta that is negative, NaN or
+ * infinite: SPMV_ACC_ERR_BAD_ARGUMENT; m or nnz beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  On the device the colouring's ONE CENSUS,
+ * counting (a) rowptr[0] != 0 or rowptr[m] != nnz, (b) rows whose rowptr extent descends or leaves [0, nnz], (c) columns outside [0, m),
+ * (d) positions where a row does not strictly ascend, (e) off-diagonal entries (i, j) whose mirror (j, i) is not stored: if any count is
+ * non-zero, SPMV_ACC_ERR_BAD_ARGUMENT, nothing was written and the error string holds the counts.  Rows are read clamped and a bad index is
+ * never turned into an address.  m == 0 touches nothing and returns 0 with *h_nnz_s = 0.  CANNOT CHECK: that theta suits the problem (with
+ * M-matrix-like values 0.25 separates a grid's strong direction from a coupling 0.01 times as large; with positive off-diagonals the
+ * criterion by magnitude may keep what a signed criterion would drop).
+ * Runs on the calling thread's library stream and has finished when it returns.  No atomic, no kernel that waits on another workgroup: two
+ * calls on the same arrays give the same arrays.  WORKSPACE, one allocation, freed on every path: 8 B per row, 8 B per entry, 96 KiB of counts
+ * and the scan's scratch.  Inside a stream capture it enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no plan.
+ * Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST: the census (one binary search per entry); one row-per-lane pass for the roots; the flags pass, one entry per lane: 12 B streamed per
+ * entry, two gathers of sd, one binary search of the mirror row and one gather of the mirror's value; a scan of nnz + 1 ints; a row-pointer
+ * pass; the scatter, 12 B read and 4 or 8 B written per entry; one synchronising read each for the census and for nnz_s.  As measured (MI355X,
+ * tools/strength_bench.py, profiles/strength_bench.md; anisotropic values of which 44 % drop at theta = 0.05): a 9-point FEM-quads matrix of
+ * 4.0 M rows and 36.0 M entries 3.09 ms = 41 settled SpMVs (spmv_acc_csr_aggregate on that pattern: 3.00 ms); a 27-point grid of 3.4 M rows and
+ * 89.9 M entries 9.34 ms = 49 SpMVs; 23 and 30 x a device copy of the inputs and outputs alone.  From a kernel trace: the flags pass 1.50 and
+ * 3.51 ms, the census 0.30 and 2.56 ms, the scatter 0.14 and 0.36 ms.  A flags pass with one row per lane was measured and not kept: 0.92 ms
+ * on the mesh, 7.52 ms on the grid. */
+int spmv_acc_csr_strength(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, double theta,
+                          int *d_s_rowptr, int *d_s_colindex, int *d_map, int *d_drop_ptr, int *h_nnz_s, int *h_no_diag);
+
+/* ---- strength of connection, 2: the lumped diagonal, the filtered matrix and the prolongator smoother (new; the per-step values pass) --------
+ * replaces: nothing in the reference.  On the arrays of spmv_acc_csr_strength and the CURRENT values of A (nnz doubles, A's order):
+ * LAUNCH 1, per row i: the lump s_i = the sum of d_value[d_map[p]] over the run [d_drop_ptr[i], d_drop_ptr[i + 1]) in the summation order of
+ *   spmv_acc_coo_to_csr_values;  d_diag[i] = a_ii with its bits copied if the run is empty, fl(a_ii + s_i) otherwise, and +0.0 if S's row holds no
+ *   diagonal (THE LUMP OF SUCH A ROW IS DISCARDED: S has no entry to carry it).  m doubles: the diagonal D_F of the filtered matrix.
+ * LAUNCH 2, per entry j of S in row i, v = d_value[d_map[j]]:
+ *   omega == 0.0: the FILTERED MATRIX A_F on S's structure: the diagonal gets d_diag[i], an off-diagonal v with its bits copied.  The row sums
+ *     of A_F are those of A up to rounding (rows with a stored diagonal).
+ *   omega != 0.0: M = I - omega D_F^-1 A_F on S's structure, so that the smoothed prolongator (I - omega D_F^-1 A_F) T is ONE
+ *     spmv_acc_csr_spgemm(M, T):  the diagonal gets d_diag[i] == 0.0 ? 1.0 : fl(1.0 - omega);  an off-diagonal gets
+ *     d_diag[i] == 0.0 ? +0.0 : fl(fl(-omega * v) / d_diag[i]).  A row with a zero d_diag is an identity row.
+ * d_s_value: nnz_s doubles.  BIT FOR BIT a pure function of the arrays and omega: no fused multiply-add, every operation rounded on its own.
+ * The maps are the caller's arrays: every run and row is clamped ([0, nnz] and [0, nnz_s]); a d_map index outside [0, nnz) gives +0.0; the row
+ * of an entry is searched inside [0, m) whatever d_s_rowptr holds: crafted arrays cannot make it read or write outside the caller's arrays.
+ * Nothing is written outside d_s_value[0 .. nnz_s) and d_diag[0 .. m).  CANNOT CHECK that the four arrays describe the same partition: pass
+ * them as spmv_acc_csr_strength left them.
+ * Two launches on the calling thread's library stream, the diagonal and then the values: asynchronous, no allocation, no synchronisation, no
+ * copy, no plan; may be captured into a hipGraph.  CHECKS, on the host, nothing launched: negative sizes, nnz_s > nnz, null pointers where data
+ * is needed, an omega that is NaN or infinite, d_value or d_diag overlapping d_s_value, d_diag overlapping d_value:
+ * SPMV_ACC_ERR_BAD_ARGUMENT; m or nnz beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  Returns 0 or an spmv_acc_error code.
+ * omega = 4 / (3 rho(D_F^-1 A_F)) is the caller's to estimate (d_diag and a few SpMVs with A_F); 2/3 suits a diagonally dominant A_F.
+ * COST: launch 1 reads 8 B per row of pointers, 12 B per dropped entry and a short search per row, and writes 8 B per row; launch 2 streams
+ * 8 B, gathers 8 B, searches its row and stores 8 B per entry of S, four entries per lane.  As measured (the same tool, file and matrices),
+ * both launches together: 0.52 ms on the FEM-quads matrix (20.0 M kept entries) = 6.9 SpMVs = 3.4 x a device copy of those bytes, 1.80 ms on
+ * the grid (50.1 M kept) = 9.4 SpMVs = 5.3 x; omega != 0 costs the same within 1 %; replayed from a graph: the same times.  From a kernel
+ * trace: launch 1 0.21 and 1.13 ms (twelve dropped entries a row on the grid: a chain of dependent gathers per lane), launch 2 0.31 and
+ * 0.71 ms.  Supposed, not checked with counters: the searches of the wavefront's two end rows over all of d_s_rowptr bound launch 2. */
+int spmv_acc_csr_strength_values(int m, int nnz, int nnz_s, const int *d_s_rowptr, const int *d_s_colindex, const int *d_map,
+                                 const int *d_drop_ptr, const double *d_value, double omega, double *d_s_value, double *d_diag);
 
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step

@@ -10,6 +10,7 @@ Reference interface mirrored (names and argument meaning): ``sparse_spmv`` (src/
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional, Sequence
 
@@ -47,6 +48,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_extract", "spmv_acc_csr_extract_values",
     "spmv_acc_csr_color", "spmv_acc_csr_gs_sweep",
     "spmv_acc_csr_aggregate", "spmv_acc_csr_tentative_values",
+    "spmv_acc_csr_strength", "spmv_acc_csr_strength_values",
 )
 
 _lib = None
@@ -175,6 +177,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_aggregate.restype = ci
     lib.spmv_acc_csr_tentative_values.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp]
     lib.spmv_acc_csr_tentative_values.restype = ci
+    lib.spmv_acc_csr_strength.argtypes = [ci, ci, vp, vp, vp, cd, vp, vp, vp, vp, _c_int_p, _c_int_p]
+    lib.spmv_acc_csr_strength.restype = ci
+    lib.spmv_acc_csr_strength_values.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, cd, vp, vp]
+    lib.spmv_acc_csr_strength_values.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -810,7 +816,7 @@ def csr_aggregate(m: int, rowptr, colindex):
     a row next to a root joins it, every other row joins the smallest aggregate among its assigned neighbours -- unique, a pure function of the
     pattern.  agg[v]: the aggregate of row v.  agg_rows: the rows in ascending (aggregate, row).  agg_ptr: naggs + 1 entries, aggregate a
     owns agg_rows[agg_ptr[a]:agg_ptr[a + 1]].  All int32 on the GPU; naggs a host int.  len(colindex) must be rowptr[m].  Synchronises; not
-    capturable.
+    capturable.  The strength graph of a value threshold is csr_strength's kept pattern (see csr_smooth_prolongator for the whole level).
 
     The Galerkin product A_c = P^T A P on the device, P from csr_tentative:
         agg, agg_ptr, agg_rows, naggs = csr_aggregate(m, rowptr, colindex)
@@ -890,6 +896,105 @@ def csr_tentative(m: int, agg, agg_ptr, agg_rows, b=None):
     csr_tentative_values(m, agg, agg_ptr, agg_rows, b, p_value, r_value, bc)
     p_rowptr = torch.arange(m + 1, dtype=torch.int32, device=dev)
     return (p_rowptr, agg, p_value), (agg_ptr, agg_rows, r_value), bc
+
+
+def csr_strength_values(m: int, s_rowptr, s_colindex, map, drop_ptr, value, s_value, diag, omega: float = 0.0) -> None:
+    """The values that go with csr_strength's kept pattern, in place (spmv_acc_csr_strength_values, async on torch's current stream,
+    capturable): diag[i] = a_ii plus the sum of row i's dropped entries (+0.0 for a row of S without a diagonal, whose lump is discarded), and
+    s_value on S's structure: omega == 0.0 the filtered matrix A_F (diag on the diagonal, A's values elsewhere, bits copied); omega != 0.0
+    M = I - omega D_F^-1 A_F (1 - omega on the diagonal, -omega * v / diag[i] elsewhere; a row with a zero diag is an identity row).
+    nnz = len(map) = len(value), nnz_s = len(s_colindex) = len(s_value), len(diag) = m.  value holds A's CURRENT values in A's order.  Bit for
+    bit a pure function of the arrays and omega.  value and diag must not overlap s_value, diag must not overlap value."""
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(s_rowptr=s_rowptr, s_colindex=s_colindex, map=map, drop_ptr=drop_ptr, value=value, s_value=s_value, diag=diag)
+    nnz, nnz_s = int(map.numel()), int(s_colindex.numel())
+    if nnz_s > nnz:
+        raise SpmvAccError(f"s_colindex holds {nnz_s} elements, map {nnz}: the kept pattern has at most as many entries as the matrix")
+    for name, t, count, what in (("value", value, nnz, f"the values of the {nnz} positions of map"),
+                                 ("s_value", s_value, nnz_s, f"the values of the {nnz_s} entries of s_colindex"),
+                                 ("diag", diag, m, f"the diagonal of the {m} rows")):
+        if int(t.numel()) != count:
+            raise SpmvAccError(f"{name} holds {int(t.numel())} elements, {what} must be as many")
+    if not math.isfinite(omega):
+        raise SpmvAccError(f"omega = {omega}: a finite relaxation factor is required")
+    _require(lib, s_rowptr=(s_rowptr, "i32", m + 1), s_colindex=(s_colindex, "i32", nnz_s), map=(map, "i32", nnz), drop_ptr=(drop_ptr, "i32", m + 1),
+             value=(value, "f64", nnz), s_value=(s_value, "f64", nnz_s), diag=(diag, "f64", m))
+    rc = lib.spmv_acc_csr_strength_values(m, nnz, nnz_s, _ptr(s_rowptr), _ptr(s_colindex) if nnz_s else 0, _ptr(map) if nnz else 0, _ptr(drop_ptr),
+                                          _ptr(value) if nnz else 0, float(omega), _ptr(s_value) if nnz_s else 0, _ptr(diag) if m else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_strength_values failed ({rc})")
+
+
+def csr_strength(m: int, rowptr, colindex, value, theta: float):
+    """The strength-of-connection filter of a square m x m CSR with strictly ascending rows and a symmetric pattern (values may be unsymmetric)
+    at the threshold theta >= 0 (spmv_acc_csr_strength): returns ((s_rowptr, s_colindex, s_value), map, drop_ptr, diag, no_diag).
+    With sd[i] = sqrt(|a_ii|) (+0.0 without a stored diagonal) an off-diagonal (i, j) is kept iff |a_ij| >= (sd[i] * sd[j]) * theta or
+    |a_ji| >= the same; a stored diagonal is always kept: a symmetric pattern whatever the values, unique to the bit.  S = (s_rowptr, s_colindex)
+    holds the kept entries in A's order -- the strength graph csr_aggregate takes --; s_value = the filtered matrix A_F, the dropped entries of a
+    row lumped onto its diagonal, which is diag (csr_strength_values with omega = 0).  map: A's positions, the kept ones ascending then the
+    dropped ones ascending; drop_ptr[i]: where row i's dropped positions begin in map.  no_diag: rows without a stored diagonal (a host int).
+    len(colindex) must be rowptr[m].  Synchronises; not capturable.  Refresh the values for new values of A with csr_strength_values."""
+    import torch
+
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(rowptr=rowptr, colindex=colindex, value=value)
+    nnz = int(colindex.numel())
+    if int(value.numel()) != nnz:
+        raise SpmvAccError(f"value holds {int(value.numel())} elements, the {nnz} entries of colindex must be as many")
+    if not (math.isfinite(theta) and theta >= 0.0):
+        raise SpmvAccError(f"theta = {theta}: a finite threshold >= 0 is required")
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0), value=(value, "f64", 0))
+    dev = rowptr.device
+    s_rowptr = torch.zeros(m + 1, dtype=torch.int32, device=dev)  # (no rows: [0], the entry touches nothing)
+    drop_ptr = torch.zeros(m + 1, dtype=torch.int32, device=dev)
+    s_colindex = torch.empty(nnz, dtype=torch.int32, device=dev)
+    map = torch.empty(nnz, dtype=torch.int32, device=dev)
+    h_nnz_s, h_no_diag = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.spmv_acc_csr_strength(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(value) if nnz else 0, float(theta), _ptr(s_rowptr) if m else 0,
+                                   _ptr(s_colindex) if nnz else 0, _ptr(map) if nnz else 0, _ptr(drop_ptr) if m else 0, ctypes.byref(h_nnz_s),
+                                   ctypes.byref(h_no_diag))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_strength failed ({rc})")
+    nnz_s = int(h_nnz_s.value)
+    s_colindex = s_colindex[:nnz_s]
+    s_value = torch.empty(nnz_s, dtype=torch.float64, device=dev)
+    diag = torch.empty(m, dtype=torch.float64, device=dev)
+    csr_strength_values(m, s_rowptr, s_colindex, map, drop_ptr, value, s_value, diag, 0.0)
+    return (s_rowptr, s_colindex, s_value), map, drop_ptr, diag, int(h_no_diag.value)
+
+
+def csr_smooth_prolongator(m: int, naggs: int, s_rowptr, s_colindex, map, drop_ptr, value, P, omega: float):
+    """The prolongator of smoothed aggregation, P_s = (I - omega D_F^-1 A_F) T, as a CSR (p_rowptr, p_colindex, p_value) of m x naggs:
+    csr_strength_values(..., omega) into a fresh value array M on S's structure, then csr_spgemm(m, m, naggs, s_rowptr, s_colindex, M, *P).
+    P = (t_rowptr, t_colindex, t_value) is the tentative prolongator T of csr_tentative; value holds A's values in A's order.
+
+    One level of an aggregation AMG setup on the device:
+        S, map, drop_ptr, diag, _ = csr_strength(m, rowptr, colindex, value, theta)     # S = (s_rowptr, s_colindex, A_F's values)
+        agg, agg_ptr, agg_rows, naggs = csr_aggregate(m, S[0], S[1])                      # aggregates of the strength graph
+        T, _, bc = csr_tentative(m, agg, agg_ptr, agg_rows, b)
+        Ps = csr_smooth_prolongator(m, naggs, S[0], S[1], map, drop_ptr, value, T, omega)
+        Rs = csr_transpose(m, naggs, Ps[1].numel(), *Ps)                                  # R = P_s^T
+        AP = csr_spgemm(m, m, naggs, rowptr, colindex, value, *Ps)
+        c_rowptr, c_colindex, c_value = csr_spgemm(naggs, m, naggs, *Rs, *AP)             # A_c = R A P_s; bc: the next level's b
+    omega = 4 / (3 rho(D_F^-1 A_F)) is the caller's to estimate, with diag and the SpMV on A_F (a few power iterations); 2/3 suits a
+    diagonally dominant A_F.  (omega = 0 would multiply T by A_F itself, which is no prolongator: pass the omega of the smoother.)"""
+    import torch
+
+    if m < 0 or naggs < 0:
+        raise SpmvAccError(f"negative shape ({m}, {naggs})")
+    _require_tensors(s_colindex=s_colindex)
+    if not isinstance(P, (tuple, list)) or len(P) != 3:
+        raise SpmvAccError("P: the tentative prolongator as (p_rowptr, p_colindex, p_value) is required")
+    m_value = torch.empty(int(s_colindex.numel()), dtype=torch.float64, device=s_colindex.device)
+    diag = torch.empty(m, dtype=torch.float64, device=s_colindex.device)
+    csr_strength_values(m, s_rowptr, s_colindex, map, drop_ptr, value, m_value, diag, omega)
+    return csr_spgemm(m, m, naggs, s_rowptr, s_colindex, m_value, *P)
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:

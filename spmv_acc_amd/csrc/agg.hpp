@@ -9,7 +9,7 @@
 // THE AGGREGATES (a pure function of the pattern; tests/test_agg_host.py host_csr_aggregate restates it in numpy).  The input is the pattern of the
 // STRENGTH GRAPH: square m x m, rebased CSR, rows strictly ascending, pattern symmetric -- the colouring's contract (gs.hpp), checked by the
 // colouring's census; a stored diagonal is not required and values are not read.  For the matrix itself that is its own pattern; a filter that
-// drops weak entries by a value threshold is OUT OF SCOPE here: the caller filters (csr_extract keeps any sub-pattern) and passes what is left.
+// drops weak entries by a value threshold is OUT OF SCOPE here: spmv_acc_csr_strength (strength.hpp) does it, and its kept pattern is what is passed.
 // Row v has the priority gs_priority(v) of gs.hpp.  Distances are counted over off-diagonal entries.
 //   ROOTS.  The rows are taken in DESCENDING priority; a row becomes a root if no root already chosen lies within distance 2 of it: the
 //           lexicographically first distance-2 maximal independent set.  An isolated row is a root.

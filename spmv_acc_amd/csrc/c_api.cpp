@@ -20,6 +20,7 @@
 #include "extract.hpp"
 #include "gs.hpp"
 #include "agg.hpp"
+#include "strength.hpp"
 
 #include <string>
 #include <cstdint>
@@ -283,6 +284,16 @@ int spmv_acc_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_col
 int spmv_acc_csr_tentative_values(int m, int naggs, const int *d_agg, const int *d_agg_ptr, const int *d_agg_rows, const double *d_b,
                                   double *d_p_value, double *d_r_value, double *d_bc) {
   return run_csr_tentative_values(m, naggs, d_agg, d_agg_ptr, d_agg_rows, d_b, d_p_value, d_r_value, d_bc);
+}
+
+int spmv_acc_csr_strength(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, double theta, int *d_s_rowptr,
+                          int *d_s_colindex, int *d_map, int *d_drop_ptr, int *h_nnz_s, int *h_no_diag) {
+  return run_csr_strength(m, nnz, d_rowptr, d_colindex, d_value, theta, d_s_rowptr, d_s_colindex, d_map, d_drop_ptr, h_nnz_s, h_no_diag);
+}
+
+int spmv_acc_csr_strength_values(int m, int nnz, int nnz_s, const int *d_s_rowptr, const int *d_s_colindex, const int *d_map,
+                                 const int *d_drop_ptr, const double *d_value, double omega, double *d_s_value, double *d_diag) {
+  return run_csr_strength_values(m, nnz, nnz_s, d_s_rowptr, d_s_colindex, d_map, d_drop_ptr, d_value, omega, d_s_value, d_diag);
 }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
