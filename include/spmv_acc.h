@@ -625,6 +625,51 @@ int spmv_acc_csr_strength(int m, int nnz, const int *d_rowptr, const int *d_coli
 int spmv_acc_csr_strength_values(int m, int nnz, int nnz_s, const int *d_s_rowptr, const int *d_s_colindex, const int *d_map,
                                  const int *d_drop_ptr, const double *d_value, double omega, double *d_s_value, double *d_diag);
 
+/* ---- dense coarse-level solve, 1: the inverse of a small CSR by Gauss-Jordan elimination (new; analysis) -------------------------------------
+ * replaces: nothing in the reference.  The solve on the coarsest level of a multigrid hierarchy, on the device: d_inv = A^-1 as a dense
+ * row-major m x m array, which spmv_acc_dense_apply multiplies by a right-hand side per cycle.
+ * INPUTS: A, m x m, CSR, int32 / fp64, rebased (rowptr[0] == 0, rowptr[m] == nnz); its rows STRICTLY ascend, its columns lie in [0, m); the
+ * pattern need not be symmetric.  m <= 4096.  d_inv: caller-owned, m * m doubles.
+ * THE RESULT IS UNIQUE TO THE BIT (-0.0 and +0.0 count as equal, NaNs by position), a pure function of the arrays: E = [A | I], m x 2m,
+ * positions not stored +0.0; for k = 0 .. m - 1: the pivot row p = the smallest i in [k, m) whose |E[i, k]| equals the maximum over the non-NaN
+ * magnitudes of E[k .. m - 1, k] (all NaN: p = k); rows k and p are swapped; piv = E[k, k]; E[k, j] = E[k, j] / piv for every j (an IEEE
+ * division, not a reciprocal multiply); every row i != k, with f = E[i, k] taken before the row changes: E[i, j] = fl(E[i, j] - fl(f * E[k, j]))
+ * (no fused multiply-add).  d_inv = the right half of E.  The elimination is NOT blocked: the unblocked order is the definition
+ * (spmv_acc_amd/csrc/dense.hpp spells it out, tests/test_dense_host.py host_dense_inverse restates it in numpy).
+ * *h_info = 0: the inverse is valid.  *h_info = k + 1: the pivot of step k, the first such, was zero, NaN or infinite -- A is singular to
+ * working precision, or holds a non-finite value --; the elimination is carried out all the same and the contents of d_inv are unspecified.
+ * CHECKS.  On the host, before the device is touched: negative m or nnz, null pointers where data is needed: SPMV_ACC_ERR_BAD_ARGUMENT;
+ * m > 4096 or nnz beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  On the device the colouring's ONE CENSUS, counting (a) rowptr[0] != 0 or
+ * rowptr[m] != nnz, (b) rows whose rowptr extent descends or leaves [0, nnz], (c) columns outside [0, m), (d) positions where a row does not
+ * strictly ascend: if any count is non-zero, SPMV_ACC_ERR_BAD_ARGUMENT, nothing was written and the error string holds the counts.  Rows are
+ * read clamped and a bad index is never turned into an address.  m == 0 reads nothing, writes nothing and sets *h_info = 0.
+ * CANNOT CHECK: that the inverse is accurate.  Partial pivoting bounds the growth in practice, not in theory, and an ill-conditioned A gives
+ * an inverse with few correct digits and *h_info = 0: max |A inv - I| is of the order m cond(A) 2^-52.
+ * Runs on the calling thread's library stream and has finished when it returns.  No atomic, no kernel that waits on another workgroup: two
+ * calls on the same arrays give the same bits.  WORKSPACE, one allocation, freed on every path: 16 m B per row (E), 24 B per row and 96 KiB of
+ * counts: 256 MiB at 4096 rows.  Inside a stream capture it enqueues nothing and returns SPMV_ACC_ERR_BAD_ARGUMENT.  Makes and touches no
+ * plan.  Returns 0 or an spmv_acc_error code (also left in spmv_acc_last_error).
+ * COST: 3 m + 4 launches -- per step the pivot search (one workgroup), the row pass and the rank-1 update, which reads and writes all of E:
+ * 32 m^3 B of traffic in all, and below a few hundred rows nothing but launches.  As measured (MI355X,
+ * tools/amg_bench.py, profiles/amg_bench.md; the five-point Laplacian): 64 rows 0.7 ms, 256 rows 2.2 to 2.5 ms, 1024 rows 12.5 ms -- 9 to 12 us per
+ * step, three launches, at all three sizes: launches, not bytes.  The cap of 4096 rows is reasoned from memory, not timed. */
+int spmv_acc_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, double *d_inv, int *h_info);
+
+/* ---- dense coarse-level solve, 2: the apply (new; the per-step hot path) ---------------------------------------------------------------------
+ * replaces: nothing in the reference.  d_x = d_inv d_b with the row-major m x m array of spmv_acc_csr_dense_inverse (or any other).
+ * BIT FOR BIT a pure function of the arrays: x[i] is the sum of the terms inv[i, j] * b[j], each product rounded on its own (no fused
+ * multiply-add), added by the 64 lanes of one wavefront: lane l the terms l, l + 64, ... in order from its first (a lane without a term
+ * holds +0.0), the 64 partial sums as a balanced tree over neighbouring lanes -- the order of spmv_acc_csr_gs_sweep with G = 64.  It does not
+ * depend on the grid or on timing.
+ * One launch on the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy, no plan; may be captured
+ * into a hipGraph.  m == 0 launches nothing.  CHECKS, on the host, nothing launched: a negative m, null pointers where data is needed, d_b
+ * overlapping d_x, either overlapping d_inv: SPMV_ACC_ERR_BAD_ARGUMENT; m beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  Returns 0 or an
+ * spmv_acc_error code.  CANNOT CHECK: that d_inv holds m * m doubles, or the inverse of the matrix the caller means.
+ * COST: 8 m^2 B of inv read once, one wavefront per row in 512-B lines; b (8 m B) is read by every wavefront and served by the cache.
+ * As measured (the same tool and file): 0.009 ms at 64, 256 and 1024 rows alike, plain or replayed from a graph (0.010 ms) -- one launch --,
+ * 2.3 to 2.7 x torch's device copy of as many bytes, which is one launch as well (0.004 ms).  Larger inverses were not measured. */
+int spmv_acc_dense_apply(int m, const double *d_inv, const double *d_b, double *d_x);
+
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step
  * (spmv_acc_shard_step with pipeline > 1, spmv_acc_amd/dist.py): rows [row_cuts[k], row_cuts[k + 1]) of the matrix are chunk k,

@@ -49,6 +49,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_color", "spmv_acc_csr_gs_sweep",
     "spmv_acc_csr_aggregate", "spmv_acc_csr_tentative_values",
     "spmv_acc_csr_strength", "spmv_acc_csr_strength_values",
+    "spmv_acc_csr_dense_inverse", "spmv_acc_dense_apply",
 )
 
 _lib = None
@@ -181,6 +182,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_strength.restype = ci
     lib.spmv_acc_csr_strength_values.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, cd, vp, vp]
     lib.spmv_acc_csr_strength_values.restype = ci
+    lib.spmv_acc_csr_dense_inverse.argtypes = [ci, ci, vp, vp, vp, vp, _c_int_p]
+    lib.spmv_acc_csr_dense_inverse.restype = ci
+    lib.spmv_acc_dense_apply.argtypes = [ci, vp, vp, vp]
+    lib.spmv_acc_dense_apply.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -983,7 +988,8 @@ def csr_smooth_prolongator(m: int, naggs: int, s_rowptr, s_colindex, map, drop_p
         AP = csr_spgemm(m, m, naggs, rowptr, colindex, value, *Ps)
         c_rowptr, c_colindex, c_value = csr_spgemm(naggs, m, naggs, *Rs, *AP)             # A_c = R A P_s; bc: the next level's b
     omega = 4 / (3 rho(D_F^-1 A_F)) is the caller's to estimate, with diag and the SpMV on A_F (a few power iterations); 2/3 suits a
-    diagonally dominant A_F.  (omega = 0 would multiply T by A_F itself, which is no prolongator: pass the omega of the smoother.)"""
+    diagonally dominant A_F.  (omega = 0 would multiply T by A_F itself, which is no prolongator: pass the omega of the smoother.)
+    spmv_acc_amd.amg.amg_setup runs this recipe level by level down to a dense coarsest solve, and amg_cycle applies the V-cycle."""
     import torch
 
     if m < 0 or naggs < 0:
@@ -995,6 +1001,58 @@ def csr_smooth_prolongator(m: int, naggs: int, s_rowptr, s_colindex, map, drop_p
     diag = torch.empty(m, dtype=torch.float64, device=s_colindex.device)
     csr_strength_values(m, s_rowptr, s_colindex, map, drop_ptr, value, m_value, diag, omega)
     return csr_spgemm(m, m, naggs, s_rowptr, s_colindex, m_value, *P)
+
+
+DENSE_MAX_ROWS = 4096  # kDenseMaxRows (spmv_acc_amd/csrc/dense.hpp): the rows csr_dense_inverse takes
+
+
+def csr_dense_inverse(m: int, rowptr, colindex, value):
+    """The dense inverse of a small square m x m CSR with strictly ascending rows (spmv_acc_csr_dense_inverse), m <= DENSE_MAX_ROWS: returns
+    (inv, info).  inv: a torch fp64 tensor of shape (m, m) on the GPU, row-major, by Gauss-Jordan elimination with partial pivoting in the
+    unblocked order include/spmv_acc.h documents -- a pure function of the arrays, bit for bit.  info == 0: inv is valid; info == k + 1: the
+    pivot of step k was zero, NaN or infinite (a singular matrix) and inv is unspecified.  The pattern need not be symmetric.  len(colindex)
+    and len(value) must be rowptr[m].  Synchronises; not capturable.  3 m launches: the solve of the coarsest level of a hierarchy, computed
+    once; dense_apply multiplies by it per cycle."""
+    import torch
+
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(rowptr=rowptr, colindex=colindex, value=value)
+    nnz = int(colindex.numel())
+    if int(value.numel()) != nnz:
+        raise SpmvAccError(f"value holds {int(value.numel())} elements, the {nnz} entries of colindex must be as many")
+    if m > DENSE_MAX_ROWS:
+        raise SpmvAccError(f"{m} rows: csr_dense_inverse takes at most {DENSE_MAX_ROWS} (too large for a dense inverse: coarsen further)")
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0), value=(value, "f64", 0))
+    inv = torch.empty((m, m), dtype=torch.float64, device=rowptr.device)
+    h_info = ctypes.c_int(0)
+    rc = lib.spmv_acc_csr_dense_inverse(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(value) if nnz else 0, _ptr(inv) if m else 0,
+                                        ctypes.byref(h_info))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_dense_inverse failed ({rc})")
+    return inv, int(h_info.value)
+
+
+def dense_apply(m: int, inv, b, x) -> None:
+    """x = inv b with the (m, m) row-major inverse of csr_dense_inverse (spmv_acc_dense_apply, async on torch's current stream, capturable):
+    one wavefront per row, the products rounded on their own and added in csr_gs_sweep's order with a lane group of 64 -- bit for bit a pure
+    function of the arrays.  b, x: m fp64 entries each; b must not overlap x, and neither may overlap inv."""
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    _require_tensors(inv=inv, b=b, x=x)
+    if int(inv.numel()) != m * m:
+        raise SpmvAccError(f"inv holds {int(inv.numel())} elements, the inverse of {m} rows must hold {m * m}")
+    for name, t in (("b", b), ("x", x)):
+        if int(t.numel()) != m:
+            raise SpmvAccError(f"{name} holds {int(t.numel())} elements, a vector of the {m} rows must hold as many")
+    _require(lib, inv=(inv, "f64", m * m), b=(b, "f64", m), x=(x, "f64", m))
+    rc = lib.spmv_acc_dense_apply(m, _ptr(inv) if m else 0, _ptr(b) if m else 0, _ptr(x) if m else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"dense_apply failed ({rc})")
 
 
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:
@@ -1222,3 +1280,6 @@ def set_strategy(name: str) -> None:
 def get_strategy() -> str:
     lib = load_library()
     return lib.spmv_acc_strategy_name(lib.spmv_acc_get_strategy()).decode()
+
+
+from .amg import AmgHierarchy, amg_cycle, amg_setup  # noqa: E402  (the hierarchy and the V-cycle, composed from the entries above)

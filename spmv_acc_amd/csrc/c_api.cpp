@@ -21,6 +21,7 @@
 #include "gs.hpp"
 #include "agg.hpp"
 #include "strength.hpp"
+#include "dense.hpp"
 
 #include <string>
 #include <cstdint>
@@ -295,6 +296,12 @@ int spmv_acc_csr_strength_values(int m, int nnz, int nnz_s, const int *d_s_rowpt
                                  const int *d_drop_ptr, const double *d_value, double omega, double *d_s_value, double *d_diag) {
   return run_csr_strength_values(m, nnz, nnz_s, d_s_rowptr, d_s_colindex, d_map, d_drop_ptr, d_value, omega, d_s_value, d_diag);
 }
+
+int spmv_acc_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, double *d_inv, int *h_info) {
+  return run_csr_dense_inverse(m, nnz, d_rowptr, d_colindex, d_value, d_inv, h_info);
+}
+
+int spmv_acc_dense_apply(int m, const double *d_inv, const double *d_b, double *d_x) { return run_dense_apply(m, d_inv, d_b, d_x); }
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
                              const int *d_rowptr, const int *d_colindex, const double *d_value, const double *dx,
