@@ -5,47 +5,30 @@
 // hands it back to the apply.  The apply is launch-only: one kernel, nothing else.
 #include "dense.hpp"
 #include "engine_internal.hpp"
+#include "entry_helpers.hpp"
 
 namespace spmv_acc {
 
 using namespace detail;
 
-namespace {
-
-int dense_error(const char *entry, int code, const std::string &what) {
-  set_error(code, std::string(entry) + ": " + what);
-  return code;
-}
-
-constexpr size_t kDenseAlign = 256; // workspace parts start on 256-B boundaries
-size_t dense_aligned_up(size_t b) { return (b + kDenseAlign - 1) / kDenseAlign * kDenseAlign; }
-
-// the sizes every entry of the library accepts (plan.cpp: room for block arithmetic in int32)
-bool dense_too_large(long long v) { return v > INT_MAX - (1 << 16); }
-
-// [a, a + na) and [b, b + nb) share a byte (doubles; a null array shares nothing)
-bool dense_overlap(const double *a, long long na, const double *b, long long nb) { return a && b && na > 0 && nb > 0 && a < b + nb && b < a + na; }
-
-} // namespace
-
 int run_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, double *d_inv, int *h_info) {
   static const char *const kEntry = "spmv_acc_csr_dense_inverse";
   clear_error();
   apply_env_tunables();
-  if (m < 0 || nnz < 0) return dense_error(kEntry, kErrBadArgument, "negative m or nnz");
-  if (!h_info) return dense_error(kEntry, kErrBadArgument, "null h_info");
-  if (m > 0 && (!d_rowptr || !d_inv)) return dense_error(kEntry, kErrBadArgument, "null rowptr / inv");
-  if (m > 0 && nnz > 0 && (!d_colindex || !d_value)) return dense_error(kEntry, kErrBadArgument, "null colindex / value of a matrix with non-zeros");
+  if (m < 0 || nnz < 0) return entry_error(kEntry, kErrBadArgument, "negative m or nnz");
+  if (!h_info) return entry_error(kEntry, kErrBadArgument, "null h_info");
+  if (m > 0 && (!d_rowptr || !d_inv)) return entry_error(kEntry, kErrBadArgument, "null rowptr / inv");
+  if (m > 0 && nnz > 0 && (!d_colindex || !d_value)) return entry_error(kEntry, kErrBadArgument, "null colindex / value of a matrix with non-zeros");
   if (m > kDenseMaxRows)
-    return dense_error(kEntry, kErrTooLarge, std::to_string(m) + " rows, the dense inverse takes at most " + std::to_string(kDenseMaxRows) +
+    return entry_error(kEntry, kErrTooLarge, std::to_string(m) + " rows, the dense inverse takes at most " + std::to_string(kDenseMaxRows) +
                                                  " (128 MiB of inverse, 256 MiB of workspace): coarsen further");
-  if (dense_too_large(nnz)) return dense_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32");
+  if (too_large(nnz)) return entry_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32");
   hipStream_t st = t_stream;
   note_stream_use();
   const ScopedSet<bool> capture_flag(t_capturing, stream_capturing(st));
   if (!plan_work_allowed("the dense inverse's workspace")) return last_error_code_only();
   if (m == 0) {
-    if (nnz > 0) return dense_error(kEntry, kErrBadArgument, "nnz is not rowptr[m], which is 0 without rows");
+    if (nnz > 0) return entry_error(kEntry, kErrBadArgument, "nnz is not rowptr[m], which is 0 without rows");
     *h_info = 0;
     return kOk;
   }
@@ -61,9 +44,9 @@ int run_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_coli
     return code;
   };
   const size_t rows = static_cast<size_t>(m);
-  const size_t slots_bytes = dense_aligned_up(sizeof(unsigned) * kGsCounts * kCooCheckSlots), state_bytes = dense_aligned_up(sizeof(unsigned long long) * kDenseState),
-               prow_bytes = dense_aligned_up(sizeof(double) * 2 * rows), f_bytes = dense_aligned_up(sizeof(double) * rows),
-               e_bytes = dense_aligned_up(sizeof(double) * 2 * rows * rows);
+  const size_t slots_bytes = aligned_up(sizeof(unsigned) * kGsCounts * kCooCheckSlots), state_bytes = aligned_up(sizeof(unsigned long long) * kDenseState),
+               prow_bytes = aligned_up(sizeof(double) * 2 * rows), f_bytes = aligned_up(sizeof(double) * rows),
+               e_bytes = aligned_up(sizeof(double) * 2 * rows * rows);
   const size_t off_state = slots_bytes, off_prow = off_state + state_bytes, off_f = off_prow + prow_bytes, off_e = off_f + f_bytes;
   if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&ws), off_e + e_bytes), "hipMalloc dense inverse workspace")) return leave(last_error_code_only());
   unsigned *d_slots = reinterpret_cast<unsigned *>(ws);
@@ -73,23 +56,7 @@ int run_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_coli
   double *E = reinterpret_cast<double *>(ws + off_e);
 
   // the census, before anything is written (the colouring's; its fifth count, the mirrors, is not judged: the pattern need not be symmetric)
-  std::vector<unsigned> slots(static_cast<size_t>(kGsCounts) * kCooCheckSlots, 0u);
-  bool ok = hip_ok(hipMemsetAsync(d_slots, 0, sizeof(unsigned) * kGsCounts * kCooCheckSlots, st), "zero the census");
-  if (ok) {
-    launch_gs_census(st, m, nnz, d_rowptr, d_colindex, d_slots);
-    ok = hip_ok(hipMemcpyAsync(slots.data(), d_slots, sizeof(unsigned) * kGsCounts * kCooCheckSlots, hipMemcpyDeviceToHost, st), "read the census") &&
-         hip_ok(hipStreamSynchronize(st), "census");
-  }
-  if (!ok) return leave(last_error_code_only());
-  unsigned long long bad[kGsCounts] = {0, 0, 0, 0, 0, 0};
-  for (int g = 0; g < kGsCounts; ++g)
-    for (int s = 0; s < kCooCheckSlots; ++s) bad[g] += slots[static_cast<size_t>(g) * kCooCheckSlots + s];
-  if (bad[0] + bad[1] + bad[2] + bad[3] != 0) {
-    return leave(dense_error(kEntry, kErrBadArgument,
-                             std::to_string(bad[0]) + " ends of rowptr that are not 0 and nnz, " + std::to_string(bad[1]) +
-                                 " rows with a descending or out-of-range rowptr extent, " + std::to_string(bad[2]) + " columns outside [0, m), " +
-                                 std::to_string(bad[3]) + " positions where a row does not strictly ascend: nothing was written"));
-  }
+  if (const int rc = pattern_census(st, kEntry, m, nnz, d_rowptr, d_colindex, d_slots, nullptr, nullptr)) return leave(rc);
 
   // E = [A | I]; the steps, three launches each, in the order of the definition; the right half; info, read once
   if (!hip_ok(hipMemsetAsync(state, 0, sizeof(unsigned long long) * kDenseState, st), "zero the step's state")) return leave(last_error_code_only());
@@ -102,12 +69,12 @@ int run_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_coli
   }
   launch_dense_copy(st, m, E, d_inv);
   const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(dense_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
   unsigned long long info = 0;
   if (!hip_ok(hipMemcpyAsync(&info, state + 2, sizeof(info), hipMemcpyDeviceToHost, st), "read info") || !hip_ok(hipStreamSynchronize(st), "dense inverse"))
     return leave(last_error_code_only());
   if (info > static_cast<unsigned long long>(m)) // (cannot happen: a step number)
-    return leave(dense_error(kEntry, kErrHip, "the elimination returned the step " + std::to_string(info)));
+    return leave(entry_error(kEntry, kErrHip, "the elimination returned the step " + std::to_string(info)));
   *h_info = static_cast<int>(info);
   return leave(kOk);
 }
@@ -116,18 +83,18 @@ int run_dense_apply(int m, const double *d_inv, const double *d_b, double *d_x) 
   static const char *const kEntry = "spmv_acc_dense_apply";
   clear_error();
   apply_env_tunables();
-  if (m < 0) return dense_error(kEntry, kErrBadArgument, "negative m");
-  if (m > 0 && (!d_inv || !d_b || !d_x)) return dense_error(kEntry, kErrBadArgument, "null inv / b / x");
-  if (dense_too_large(m)) return dense_error(kEntry, kErrTooLarge, "m does not leave room for block arithmetic in int32");
+  if (m < 0) return entry_error(kEntry, kErrBadArgument, "negative m");
+  if (m > 0 && (!d_inv || !d_b || !d_x)) return entry_error(kEntry, kErrBadArgument, "null inv / b / x");
+  if (too_large(m)) return entry_error(kEntry, kErrTooLarge, "m does not leave room for block arithmetic in int32");
   const long long mm = static_cast<long long>(m) * m;
-  if (dense_overlap(d_b, m, d_x, m)) return dense_error(kEntry, kErrBadArgument, "b overlaps x");
-  if (dense_overlap(d_inv, mm, d_x, m) || dense_overlap(d_inv, mm, d_b, m)) return dense_error(kEntry, kErrBadArgument, "b or x overlaps inv");
+  if (overlap(d_b, m, d_x, m)) return entry_error(kEntry, kErrBadArgument, "b overlaps x");
+  if (overlap(d_inv, mm, d_x, m) || overlap(d_inv, mm, d_b, m)) return entry_error(kEntry, kErrBadArgument, "b or x overlaps inv");
   if (m == 0) return kOk; // no rows: nothing to launch
   hipStream_t st = t_stream;
   note_stream_use();
   launch_dense_apply(st, m, d_inv, d_b, d_x);
   const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return dense_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
+  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
   return kOk;
 }
 

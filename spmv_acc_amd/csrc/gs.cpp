@@ -5,44 +5,30 @@
 // hands them back to the sweep.  The sweep is launch-only: one kernel per non-empty colour, nothing else.
 #include "gs.hpp"
 #include "engine_internal.hpp"
+#include "entry_helpers.hpp"
 
 namespace spmv_acc {
 
 using namespace detail;
-
-namespace {
-
-int gs_error(const char *entry, int code, const std::string &what) {
-  set_error(code, std::string(entry) + ": " + what);
-  return code;
-}
-
-constexpr size_t kGsAlign = 256; // workspace parts start on 256-B boundaries
-size_t gs_aligned_up(size_t b) { return (b + kGsAlign - 1) / kGsAlign * kGsAlign; }
-
-// the sizes every entry of the library accepts (plan.cpp: room for block arithmetic in int32)
-bool gs_too_large(long long v) { return v > INT_MAX - (1 << 16); }
-
-} // namespace
 
 int run_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, int *d_color, int *d_color_rows, int cap_colors, int *h_color_ptr,
                   int *h_ncolors, int *h_no_diag) {
   static const char *const kEntry = "spmv_acc_csr_color";
   clear_error();
   apply_env_tunables();
-  if (m < 0 || nnz < 0) return gs_error(kEntry, kErrBadArgument, "negative m or nnz");
-  if (cap_colors < 1) return gs_error(kEntry, kErrBadArgument, "cap_colors < 1");
-  if (!h_color_ptr || !h_ncolors || !h_no_diag) return gs_error(kEntry, kErrBadArgument, "null h_color_ptr / h_ncolors / h_no_diag");
-  if (m > 0 && (!d_rowptr || !d_color || !d_color_rows)) return gs_error(kEntry, kErrBadArgument, "null rowptr / color / color_rows");
-  if (m > 0 && nnz > 0 && !d_colindex) return gs_error(kEntry, kErrBadArgument, "null colindex of a matrix with non-zeros");
-  if (gs_too_large(m) || gs_too_large(nnz))
-    return gs_error(kEntry, kErrTooLarge, "m or nnz does not leave room for block arithmetic in int32");
+  if (m < 0 || nnz < 0) return entry_error(kEntry, kErrBadArgument, "negative m or nnz");
+  if (cap_colors < 1) return entry_error(kEntry, kErrBadArgument, "cap_colors < 1");
+  if (!h_color_ptr || !h_ncolors || !h_no_diag) return entry_error(kEntry, kErrBadArgument, "null h_color_ptr / h_ncolors / h_no_diag");
+  if (m > 0 && (!d_rowptr || !d_color || !d_color_rows)) return entry_error(kEntry, kErrBadArgument, "null rowptr / color / color_rows");
+  if (m > 0 && nnz > 0 && !d_colindex) return entry_error(kEntry, kErrBadArgument, "null colindex of a matrix with non-zeros");
+  if (too_large(m) || too_large(nnz))
+    return entry_error(kEntry, kErrTooLarge, "m or nnz does not leave room for block arithmetic in int32");
   hipStream_t st = t_stream;
   note_stream_use();
   const ScopedSet<bool> capture_flag(t_capturing, stream_capturing(st));
   if (!plan_work_allowed("the colouring's workspace")) return last_error_code_only();
   if (m == 0) {
-    if (nnz > 0) return gs_error(kEntry, kErrBadArgument, "nnz is not rowptr[m], which is 0 without rows");
+    if (nnz > 0) return entry_error(kEntry, kErrBadArgument, "nnz is not rowptr[m], which is 0 without rows");
     h_color_ptr[0] = 0;
     *h_ncolors = 0;
     *h_no_diag = 0;
@@ -64,14 +50,14 @@ int run_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, in
   size_t sort_bytes = 0;
   if (!launch_coo_sort(st, nullptr, m, key_bits, nullptr, nullptr, nullptr, &sort_bytes)) {
     (void)hipGetLastError();
-    return gs_error(kEntry, kErrHip, "radix sort workspace query failed");
+    return entry_error(kEntry, kErrHip, "radix sort workspace query failed");
   }
   const size_t rows = static_cast<size_t>(m);
-  const size_t slots_bytes = gs_aligned_up(sizeof(unsigned) * kGsCounts * kCooCheckSlots), ints = gs_aligned_up(sizeof(int) * rows),
-               keys_bytes = gs_aligned_up(sizeof(unsigned long long) * rows), ptr_bytes = gs_aligned_up(sizeof(int) * static_cast<size_t>(ptr_count));
+  const size_t slots_bytes = aligned_up(sizeof(unsigned) * kGsCounts * kCooCheckSlots), ints = aligned_up(sizeof(int) * rows),
+               keys_bytes = aligned_up(sizeof(unsigned long long) * rows), ptr_bytes = aligned_up(sizeof(int) * static_cast<size_t>(ptr_count));
   const size_t off_other = slots_bytes, off_keys = off_other + ints, off_sorted = off_keys + keys_bytes, off_ptr = off_sorted + keys_bytes,
                off_tmp = off_ptr + ptr_bytes;
-  if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&ws), off_tmp + gs_aligned_up(sort_bytes)), "hipMalloc colouring workspace"))
+  if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&ws), off_tmp + aligned_up(sort_bytes)), "hipMalloc colouring workspace"))
     return leave(last_error_code_only());
   unsigned *d_slots = reinterpret_cast<unsigned *>(ws);
   int *other = reinterpret_cast<int *>(ws + off_other);
@@ -80,27 +66,13 @@ int run_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, in
   int *d_ptr = reinterpret_cast<int *>(ws + off_ptr);
 
   // the census, before anything is written
-  std::vector<unsigned> slots(static_cast<size_t>(kGsCounts) * kCooCheckSlots, 0u);
-  bool ok = hip_ok(hipMemsetAsync(d_slots, 0, sizeof(unsigned) * kGsCounts * kCooCheckSlots, st), "zero the census");
-  if (ok) {
-    launch_gs_census(st, m, nnz, d_rowptr, d_colindex, d_slots);
-    ok = hip_ok(hipMemcpyAsync(slots.data(), d_slots, sizeof(unsigned) * kGsCounts * kCooCheckSlots, hipMemcpyDeviceToHost, st), "read the census") &&
-         hip_ok(hipStreamSynchronize(st), "census");
-  }
-  if (!ok) return leave(last_error_code_only());
-  unsigned long long bad[kGsCounts] = {0, 0, 0, 0, 0, 0};
-  for (int g = 0; g < kGsCounts; ++g)
-    for (int s = 0; s < kCooCheckSlots; ++s) bad[g] += slots[static_cast<size_t>(g) * kCooCheckSlots + s];
-  if (bad[0] + bad[1] + bad[2] + bad[3] + bad[4] != 0) {
-    return leave(gs_error(kEntry, kErrBadArgument,
-                          std::to_string(bad[0]) + " ends of rowptr that are not 0 and nnz, " + std::to_string(bad[1]) +
-                              " rows with a descending or out-of-range rowptr extent, " + std::to_string(bad[2]) + " columns outside [0, m), " +
-                              std::to_string(bad[3]) + " positions where a row does not strictly ascend, " + std::to_string(bad[4]) +
-                              " off-diagonal entries without their mirror (colour the pattern of A + A^T instead): nothing was written"));
-  }
+  unsigned long long no_diag = 0;
+  if (const int rc = pattern_census(st, kEntry, m, nnz, d_rowptr, d_colindex, d_slots, "colour the pattern of A + A^T instead", &no_diag))
+    return leave(rc);
 
   // the rounds: the caller's array and the workspace's take turns, kGsRoundsPerRead (even) rounds between two reads
   if (!hip_ok(hipMemsetAsync(d_color, 0xFF, sizeof(int) * rows, st), "uncolour the rows")) return leave(last_error_code_only());
+  std::vector<unsigned> slots(kCooCheckSlots, 0u);
   unsigned long long remaining = static_cast<unsigned long long>(m);
   while (remaining != 0) {
     for (int r = 0; r < kGsRoundsPerRead; r += 2) {
@@ -110,11 +82,10 @@ int run_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, in
     if (!hip_ok(hipMemcpyAsync(slots.data(), d_slots, sizeof(unsigned) * kCooCheckSlots, hipMemcpyDeviceToHost, st), "read the uncoloured count") ||
         !hip_ok(hipStreamSynchronize(st), "colouring rounds"))
       return leave(last_error_code_only());
-    unsigned long long now = 0;
-    for (int s = 0; s < kCooCheckSlots; ++s) now += slots[s];
+    const unsigned long long now = slot_sum(slots.data());
     if (now >= remaining) // (cannot happen on a pattern that passed the census: the uncoloured row of highest priority never waits)
-      return leave(gs_error(kEntry, kErrHip, std::to_string(kGsRoundsPerRead) + " rounds coloured no row while " + std::to_string(now) +
-                                                 " remain: no further round is issued"));
+      return leave(entry_error(kEntry, kErrHip, std::to_string(kGsRoundsPerRead) + " rounds coloured no row while " + std::to_string(now) +
+                                                    " remain: no further round is issued"));
     remaining = now;
   }
 
@@ -123,21 +94,21 @@ int run_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, in
   std::vector<int> ptr(static_cast<size_t>(ptr_count), 0);
   launch_gs_keys(st, m, d_color, keys);
   if (!launch_coo_sort(st, keys, m, key_bits, sorted, d_color_rows, ws + off_tmp, &sort_bytes))
-    return leave(gs_error(kEntry, kErrHip, "radix sort failed"));
+    return leave(entry_error(kEntry, kErrHip, "radix sort failed"));
   launch_gs_color_ptr(st, m, sorted, ptr_count, d_ptr);
   const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(gs_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
   if (!hip_ok(hipMemcpyAsync(&last_key, sorted + (rows - 1), sizeof(last_key), hipMemcpyDeviceToHost, st), "read the largest colour") ||
       !hip_ok(hipMemcpyAsync(ptr.data(), d_ptr, sizeof(int) * static_cast<size_t>(ptr_count), hipMemcpyDeviceToHost, st), "read the colour pointer") ||
       !hip_ok(hipStreamSynchronize(st), "colouring"))
     return leave(last_error_code_only());
-  if (last_key >= static_cast<unsigned long long>(m)) return leave(gs_error(kEntry, kErrHip, "the sort returned the colour " + std::to_string(last_key)));
+  if (last_key >= static_cast<unsigned long long>(m)) return leave(entry_error(kEntry, kErrHip, "the sort returned the colour " + std::to_string(last_key)));
   const int ncolors = static_cast<int>(last_key) + 1;
   *h_ncolors = ncolors;
-  *h_no_diag = static_cast<int>(bad[5]);
+  *h_no_diag = static_cast<int>(no_diag);
   if (ncolors > cap_colors)
-    return leave(gs_error(kEntry, kErrTooLarge, std::to_string(ncolors) + " colours, h_color_ptr holds " + std::to_string(cap_colors) +
-                                                    ": color and *h_ncolors are valid, call again with a larger array"));
+    return leave(entry_error(kEntry, kErrTooLarge, std::to_string(ncolors) + " colours, h_color_ptr holds " + std::to_string(cap_colors) +
+                                                       ": color and *h_ncolors are valid, call again with a larger array"));
   for (int c = 0; c <= ncolors; ++c) h_color_ptr[c] = ptr[static_cast<size_t>(c)];
   return leave(kOk);
 }
@@ -147,18 +118,18 @@ int run_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex,
   static const char *const kEntry = "spmv_acc_csr_gs_sweep";
   clear_error();
   apply_env_tunables();
-  if (m < 0 || nnz < 0 || ncolors < 0) return gs_error(kEntry, kErrBadArgument, "negative m, nnz or ncolors");
-  if (direction < 0 || direction > 2) return gs_error(kEntry, kErrBadArgument, "direction is not 0 (forward), 1 (backward) or 2 (symmetric)");
-  if (!h_color_ptr) return gs_error(kEntry, kErrBadArgument, "null h_color_ptr");
-  if (m > 0 && (!d_rowptr || !d_b || !d_x)) return gs_error(kEntry, kErrBadArgument, "null rowptr / b / x");
-  if (m > 0 && nnz > 0 && (!d_colindex || !d_value)) return gs_error(kEntry, kErrBadArgument, "null colindex / value of a matrix with non-zeros");
-  if (gs_too_large(nnz) || gs_too_large(ncolors))
-    return gs_error(kEntry, kErrTooLarge, "nnz or ncolors does not leave room for block arithmetic in int32");
-  if (m > kGsMaxRows) return gs_error(kEntry, kErrTooLarge, "more than 2^29 rows: x is gathered through 32-bit byte offsets; sweep row blocks of the matrix");
-  if (h_color_ptr[0] != 0 || h_color_ptr[ncolors] != m) return gs_error(kEntry, kErrBadArgument, "h_color_ptr does not run from 0 to m");
+  if (m < 0 || nnz < 0 || ncolors < 0) return entry_error(kEntry, kErrBadArgument, "negative m, nnz or ncolors");
+  if (direction < 0 || direction > 2) return entry_error(kEntry, kErrBadArgument, "direction is not 0 (forward), 1 (backward) or 2 (symmetric)");
+  if (!h_color_ptr) return entry_error(kEntry, kErrBadArgument, "null h_color_ptr");
+  if (m > 0 && (!d_rowptr || !d_b || !d_x)) return entry_error(kEntry, kErrBadArgument, "null rowptr / b / x");
+  if (m > 0 && nnz > 0 && (!d_colindex || !d_value)) return entry_error(kEntry, kErrBadArgument, "null colindex / value of a matrix with non-zeros");
+  if (too_large(nnz) || too_large(ncolors))
+    return entry_error(kEntry, kErrTooLarge, "nnz or ncolors does not leave room for block arithmetic in int32");
+  if (m > kGsMaxRows) return entry_error(kEntry, kErrTooLarge, "more than 2^29 rows: x is gathered through 32-bit byte offsets; sweep row blocks of the matrix");
+  if (h_color_ptr[0] != 0 || h_color_ptr[ncolors] != m) return entry_error(kEntry, kErrBadArgument, "h_color_ptr does not run from 0 to m");
   for (int c = 0; c < ncolors; ++c)
-    if (h_color_ptr[c + 1] < h_color_ptr[c]) return gs_error(kEntry, kErrBadArgument, "h_color_ptr descends at colour " + std::to_string(c));
-  if (m > 0 && d_b < d_x + m && d_x < d_b + m) return gs_error(kEntry, kErrBadArgument, "b overlaps x");
+    if (h_color_ptr[c + 1] < h_color_ptr[c]) return entry_error(kEntry, kErrBadArgument, "h_color_ptr descends at colour " + std::to_string(c));
+  if (overlap(d_b, m, d_x, m)) return entry_error(kEntry, kErrBadArgument, "b overlaps x");
   if (m == 0) return kOk; // no rows: nothing to launch
   hipStream_t st = t_stream;
   note_stream_use();
@@ -168,7 +139,7 @@ int run_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex,
   if (direction != 0)
     for (int c = ncolors - 1; c >= 0; --c) colour(c);
   const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return gs_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
+  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
   return kOk;
 }
 

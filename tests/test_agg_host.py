@@ -19,7 +19,7 @@ import spmv_acc_amd
 from test_coo_host import LONG_RUN, SHARED, _FakeTensor, _f, _i, coo_sum_model
 from test_gs_host import TAGS as GS_TAGS
 from test_gs_host import cases as gs_cases
-from test_gs_host import csr_from_pattern, priorities, row_sum
+from test_gs_host import HELPERS, csr_from_pattern, priorities, row_sum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -79,14 +79,16 @@ AGG_SIZE_RULES = [
      [VALUES], "all ones"),
     ("r_value == NULL", CSRC + "k_agg.hip", r"if \(r_value != nullptr\) \{",
      [VALUES], "R's values are optional"),
-    ("kAggAlign", CSRC + "agg.cpp", r"constexpr size_t kAggAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [MODEL], "workspace parts are padded to 256 B (row counts that are no multiple of 64: most cases)"),
     ("no rows", CSRC + "agg.cpp", r"if \(m == 0\) \{",
      [MODEL], "m == 0: no aggregate, nothing is read or allocated"),
     ("no rows: the values", CSRC + "agg.cpp", r"if \(m == 0\) return kOk;",
      [VALUES], "nothing to launch"),
-    ("int32 block arithmetic", CSRC + "agg.cpp", r"bool agg_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      [CONTRACT, VALUES_CONTRACT], "m, nnz or naggs beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
+    ("the census is shared", CSRC + "agg.cpp", r"pattern_census\(st, kEntry, ",
+     [CONTRACT, MODEL], "the refusals and their text are entry_helpers.hpp's, the same for the four entries"),
 ]
 
 
@@ -105,7 +107,7 @@ def test_agg_size_rules_name_their_tests():
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             found += 1
             assert k in registered, f"{f}: constant {k} is not in AGG_SIZE_RULES"
-    assert found == 8
+    assert found == 7
     header = open(os.path.join(ROOT, CSRC, "agg.hpp")).read()
     assert f"constexpr int kAggRoundsPerRead = {ROUNDS_PER_READ};" in header and f"constexpr int kAggLaneGroup = {LANE_GROUP};" in header
     assert f"constexpr int kAggPerLane = {PER_LANE};" in header and LONG_RUN == 64
@@ -273,15 +275,17 @@ def test_agg_entries_keep_no_state():
     assert "plan_work_allowed(" in code.split("const auto leave = ")[0]  # (a capture is refused before anything is enqueued or allocated)
     assert "hipMalloc(" not in code.split("const auto leave = ")[0]
     after = code.split("const auto leave = ")[1].split("};", 1)[1].split("\n}\n")[0]  # (to the end of the routine that allocates)
-    for launch in ("launch_gs_census", "launch_agg_init", "launch_agg_max", "launch_agg_decide", "launch_agg_flags", "launch_coo_scan",
+    for launch in ("pattern_census", "launch_agg_init", "launch_agg_max", "launch_agg_decide", "launch_agg_flags", "launch_coo_scan",
                    "launch_agg_assign_roots", "launch_agg_assign_rest", "launch_gs_keys", "launch_coo_sort", "launch_gs_color_ptr"):
         assert launch in after, launch
     bare = [ln.strip() for ln in after.splitlines() if re.search(r"\breturn\b(?! leave\()", ln)]
     # (the one way out that may skip leave(): the scratch query before the allocation)
-    assert bare == ['return agg_error(kEntry, kErrHip, "scan / radix sort workspace query failed");'], bare
+    assert bare == ['return entry_error(kEntry, kErrHip, "scan / radix sort workspace query failed");'], bare
     # the host loop can end: one comparison guards every further group of rounds
     loop = after.split("while (remaining != 0) {")[1].split("\n  }\n")[0]
-    assert "if (now >= remaining)" in loop and "return leave(agg_error(kEntry, kErrHip" in loop and "remaining = now;" in loop
+    assert "if (now >= remaining)" in loop and "return leave(entry_error(kEntry, kErrHip" in loop and "remaining = now;" in loop
+    assert after.index("pattern_census(") < after.index("launch_agg_init(")  # the census is judged before anything is written
+    assert 'pattern_census(st, kEntry, m, nnz, d_rowptr, d_colindex, d_slots, "aggregate the pattern of A + A^T instead", ' in after
     assert "*h_naggs = naggs;" in after.split("launch_gs_color_ptr")[1]  # (written last, once everything else has run)
     values = code.split("int run_csr_tentative_values")[1]
     assert "hipMalloc" not in values and "Synchronize" not in values and "hipMemcpy" not in values and "hipMemset" not in values  # launch-only

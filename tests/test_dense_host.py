@@ -16,7 +16,7 @@ import pytest
 import spmv_acc_amd
 from test_agg_host import grid5_matrix
 from test_coo_host import SHARED, _FakeTensor, _f, _i
-from test_gs_host import row_sum
+from test_gs_host import HELPERS, row_sum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -76,7 +76,7 @@ DENSE_SIZE_RULES = [
      [APPLY], "r130: three 64-strides, the third of two lanes; r65; the tail behind the four-line step at grid18"),
     ("kDenseState", CSRC + "dense.hpp", r"constexpr int kDenseState = 3;",
      [INVERSE, INFO], "p, piv and info, zeroed before the first step"),
-    ("kDenseAlign", CSRC + "dense.cpp", r"constexpr size_t kDenseAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [INVERSE], "workspace parts are padded to 256 B (row counts that are no multiple of 16: most cases)"),
     ("no rows", CSRC + "dense.cpp", r"if \(m == 0\) \{",
      [EMPTY], "m == 0: nothing is read, written or allocated, info = 0"),
@@ -84,8 +84,10 @@ DENSE_SIZE_RULES = [
      [EMPTY], "nothing to launch"),
     ("no entries", CSRC + "k_dense.hip", r"nnz <= 0\) return;",
      [INFO], "a matrix without entries: the scatter is not launched, E = [0 | I], info = 1"),
-    ("int32 block arithmetic", CSRC + "dense.cpp", r"bool dense_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      [INVERSE_CONTRACT, APPLY_CONTRACT], "nnz (the inverse) or m (the apply) beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
+    ("the census is shared", CSRC + "dense.cpp", r"pattern_census\(st, kEntry, ",
+     [INVERSE_CONTRACT, INVERSE], "the refusals and their text are entry_helpers.hpp's, the same for the four entries; without an advice the mirrors are not judged"),
 ]
 
 
@@ -104,7 +106,7 @@ def test_dense_size_rules_name_their_tests():
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             found += 1
             assert k in registered, f"{f}: constant {k} is not in DENSE_SIZE_RULES"
-    assert found == 6
+    assert found == 5
     header = open(os.path.join(ROOT, CSRC, "dense.hpp")).read()
     assert f"constexpr int kDenseMaxRows = {MAX_ROWS};" in header and f"constexpr int kDensePivotThreads = {PIVOT_THREADS};" in header
     assert f"constexpr int kDenseTile = {TILE};" in header and f"constexpr int kDenseRowsPerBlock = {ROWS_PER_BLOCK};" in header
@@ -269,18 +271,20 @@ def test_dense_entries_keep_no_state():
     assert "plan_work_allowed(" in code.split("const auto leave = ")[0]  # (a capture is refused before anything is enqueued or allocated)
     assert "hipMalloc(" not in code.split("const auto leave = ")[0]
     after = code.split("const auto leave = ")[1].split("};", 1)[1].split("\n}\n")[0]  # (to the end of the routine that allocates)
-    launches = ("launch_gs_census", "launch_dense_fill", "launch_dense_scatter", "launch_dense_pivot", "launch_dense_row", "launch_dense_update",
+    launches = ("pattern_census", "launch_dense_fill", "launch_dense_scatter", "launch_dense_pivot", "launch_dense_row", "launch_dense_update",
                 "launch_dense_copy")
     body = after.split("hipMalloc(")[1]
     assert [body.index(s + "(st, ") for s in launches] == sorted(body.index(s + "(st, ") for s in launches)  # the passes in the documented order
     assert all(body.count(s + "(st, ") == 1 for s in launches)
-    assert body.index("nothing was written") < body.index("launch_dense_fill(")  # the census is judged before anything is written
+    assert body.index("pattern_census(") < body.index("launch_dense_fill(")  # the census is judged before anything is written
+    # ... without an advice: the mirrors are neither judged nor reported, the pattern need not be symmetric (nor is the count of diagonals asked for)
+    assert "pattern_census(st, kEntry, m, nnz, d_rowptr, d_colindex, d_slots, nullptr, nullptr)" in body
     assert not [ln for ln in after.splitlines() if re.search(r"\breturn\b(?! leave\()", ln)]  # every way out passes leave()
     loop = body.split("for (int k = 0; k < m; ++k) {")[1].split("\n  }\n")[0]
     assert "Synchronize" not in loop and "hipMemcpy" not in loop and len(re.findall(r"\blaunch_\w+\(", loop)) == 3  # a step is three launches, no read
     tail = body.split("launch_dense_copy")[1]
     assert tail.count("hipMemcpyAsync(") == 1 and tail.index("hipMemcpyAsync(&info") < tail.index("*h_info = ") < tail.index("return leave(kOk);")
-    assert body.count("hipMemcpyAsync(") == 2 and "while (" not in code  # the census and info: the host reads the elimination's state once
+    assert body.count("hipMemcpyAsync(") == 1 and "while (" not in code  # info (the census' one copy is the helper's, pinned in test_gs_host): the host reads the elimination's state once
     apply = code.split("int run_dense_apply")[1]
     assert "hipMalloc" not in apply and "Synchronize" not in apply and "hipMemcpy" not in apply and "hipMemset" not in apply  # launch-only
     assert "plan_work_allowed" not in apply and apply.count("launch_dense_apply(") == 1 and len(re.findall(r"\blaunch_\w+\(", apply)) == 1

@@ -22,6 +22,8 @@ from test_extract_host import host_csr_permute
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
 NEW_SOURCES = ("gs.hpp", "k_gs.hip", "gs.cpp")
+HELPERS = "entry_helpers.hpp"  # what the four entry files of the AMG chain share: the other features' tables name it too
+ENTRY_FILES = ("gs.cpp", "agg.cpp", "strength.cpp", "dense.cpp")
 COLOR = "test_color_is_the_host_model"
 SWEEP = "test_sweep_is_the_host_model"
 STRIDE = "test_gs_grid_stride_at_test_size"
@@ -56,7 +58,7 @@ GS_SIZE_RULES = [
      [SWEEP], "the smallest G with G * 4 * rows of the chunk >= the chunk's terms, at most 64 (star's hub: 300 terms in a chunk of one row)"),
     ("kGsMaxRows", CSRC + "gs.hpp", r"constexpr int kGsMaxRows = 1 << 29;",
      [SWEEP_CONTRACT], "more rows than 32-bit gather offsets reach: SPMV_ACC_ERR_TOO_LARGE on the host"),
-    ("kGsAlign", CSRC + "gs.cpp", r"constexpr size_t kGsAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [COLOR], "workspace parts are padded to 256 B (row counts that are no multiple of 64: most cases)"),
     ("census grid", CSRC + SHARED, r"return grid > static_cast<unsigned>\(kCooCheckBlocks\) \? static_cast<unsigned>\(kCooCheckBlocks\) : grid;",
      [STRIDE, COLOR_CONTRACT], "one count slot per wavefront of at most 1 024 workgroups"),
@@ -81,8 +83,10 @@ GS_SIZE_RULES = [
      [SWEEP], "x[i] = g without the relaxation's two roundings; else x + omega * (g - x)"),
     ("no rows", CSRC + "gs.cpp", r"if \(m == 0\) \{",
      [COLOR], "m == 0: no colour, nothing is read or allocated"),
-    ("int32 block arithmetic", CSRC + "gs.cpp", r"bool gs_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      [COLOR_CONTRACT], "m or nnz beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
+    ("the census is shared", CSRC + "gs.cpp", r"pattern_census\(st, kEntry, ",
+     [COLOR_CONTRACT, COLOR], "the refusals and their text are entry_helpers.hpp's, the same for the four entries; the count of rows without a diagonal comes back from it"),
 ]
 
 
@@ -101,7 +105,10 @@ def test_gs_size_rules_name_their_tests():
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             found += 1
             assert k in registered, f"{f}: constant {k} is not in GS_SIZE_RULES"
-    assert found == 8
+    assert found == 7
+    # ... and so is the one constant of the shared host helpers, whose census lives with the colouring
+    shared = re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, HELPERS)).read())
+    assert shared == ["kEntryAlign"] and shared[0] in registered
     header = open(os.path.join(ROOT, CSRC, "gs.hpp")).read()
     assert f"constexpr int kGsChunkRows = {CHUNK_ROWS};" in header and f"constexpr int kGsTermsPerLane = {TERMS_PER_LANE};" in header
     assert f"constexpr int kGsColorWindow = {WINDOW};" in header
@@ -273,17 +280,54 @@ def test_gs_entries_keep_no_state():
     assert "plan_work_allowed(" in code.split("const auto leave = ")[0]  # (a capture is refused before anything is enqueued or allocated)
     assert "hipMalloc(" not in code.split("const auto leave = ")[0]
     after = code.split("const auto leave = ")[1].split("};", 1)[1].split("\n}\n")[0]  # (to the end of the routine that allocates)
-    for launch in ("launch_gs_census", "launch_gs_round", "launch_gs_keys", "launch_coo_sort", "launch_gs_color_ptr"):
+    for launch in ("pattern_census", "launch_gs_round", "launch_gs_keys", "launch_coo_sort", "launch_gs_color_ptr"):
         assert launch in after, launch
     bare = [ln.strip() for ln in after.splitlines() if re.search(r"\breturn\b(?! leave\()", ln)]
     # (the one way out that may skip leave(): the scratch query before the allocation)
-    assert bare == ['return gs_error(kEntry, kErrHip, "radix sort workspace query failed");'], bare
+    assert bare == ['return entry_error(kEntry, kErrHip, "radix sort workspace query failed");'], bare
     # the host loop can end: one comparison guards every further group of rounds
     loop = after.split("while (remaining != 0) {")[1].split("\n  }\n")[0]
-    assert "if (now >= remaining)" in loop and "return leave(gs_error(kEntry, kErrHip" in loop and "remaining = now;" in loop
+    assert "if (now >= remaining)" in loop and "return leave(entry_error(kEntry, kErrHip" in loop and "remaining = now;" in loop
+    assert after.index("pattern_census(") < after.index("uncolour the rows") < after.index("launch_gs_round(")  # the census is judged before anything is written
+    assert 'pattern_census(st, kEntry, m, nnz, d_rowptr, d_colindex, d_slots, "colour the pattern of A + A^T instead", ' in after
     sweep = code.split("int run_csr_gs_sweep")[1]
     assert "hipMalloc" not in sweep and "Synchronize" not in sweep and "hipMemcpy" not in sweep and "hipMemset" not in sweep  # launch-only: capturable
     assert "plan_work_allowed" not in sweep and sweep.count("launch_gs_color(") == 1 and "launch_gs_" not in sweep.replace("launch_gs_color(", "")
+
+
+def test_entry_helpers_keep_no_state():
+    """What gs.cpp, agg.cpp, strength.cpp and dense.cpp share on the host keeps nothing either: plain inline functions, no static, no device
+    allocation; the census is one memset, one launch, one copy and one synchronise, in that order, and its refusal text stands here alone."""
+    code = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, CSRC, HELPERS)).read())
+    for word in ("get_plan", "g_plans", "t_plan_work", "t_last_plan", "tune_", "TimingPhase", "TuneTimer", "static std::", "thread_local", "g_tunables"):
+        assert word not in code, word
+    assert not re.search(r"\bstatic\b", code) and "hipMalloc" not in code and "hipFree" not in code
+    functions = re.findall(r"^(\w[\w ]*?)\b(\w+)\(", code, flags=re.M)
+    assert [name for _, name in functions] == ["entry_error", "aligned_up", "too_large", "overlap", "slot_sum", "pattern_census"], functions
+    assert all(kind.startswith("inline ") for kind, _ in functions), functions
+    census = code.split("inline int pattern_census(hipStream_t st, const char *entry, ")[1].split("\n}\n")[0]
+    calls = ("hipMemsetAsync(", "launch_gs_census(", "hipMemcpyAsync(", "hipStreamSynchronize(")
+    assert all(census.count(c) == 1 for c in calls) and [census.index(c) for c in calls] == sorted(census.index(c) for c in calls)
+    assert re.findall(r"\blaunch_\w+\(", census) == ["launch_gs_census("]
+    assert [census.index(t) for t in ('"zero the census"', '"read the census"', '"census"')] == sorted(census.index(t) for t in ('"zero the census"', '"read the census"', '"census"'))
+    assert census.count("nothing was written") == 1 and census.count("ends of rowptr that are not 0 and nnz") == 1
+    # the mirrors are judged and reported under the advice's null check alone
+    assert census.count("bad[4]") == 2 and census.count("without their mirror") == 1
+    assert "(mirror_advice ? bad[4] : 0)" in census
+    clause = next(ln for ln in census.splitlines() if "without their mirror" in ln)
+    assert clause.strip().startswith("if (mirror_advice) what += ") and "bad[4]" in clause and '" + mirror_advice + ")"' in clause
+    assert census.index("without their mirror") < census.index("nothing was written")
+    assert census.count("if (no_diag) *no_diag = bad[5];") == 1 and census.count("bad[5]") == 1
+    # the copies are gone from the four entry files, and the refusal's text with them
+    for f in ENTRY_FILES:
+        entry = open(os.path.join(ROOT, CSRC, f)).read()
+        assert '#include "' + HELPERS + '"' in entry, f
+        for gone in ("launch_gs_census(", "bad[kGsCounts]", "ends of rowptr", "nothing was written", "kCooCheckSlots; ++s"):
+            assert gone not in entry, (f, gone)
+        assert not re.search(r"\b(gs|agg|strength|dense)_(error|too_large|aligned_up|overlap)\(", entry), f
+        assert set(re.findall(r"\b(\w*(?:too_large|aligned_up|overlap))\(", entry)) <= {"too_large", "aligned_up", "overlap"}, f
+        assert not re.search(r"constexpr size_t k\w*Align", entry), f
+    assert HELPERS in open(os.path.join(ROOT, CSRC, "Makefile")).read()
 
 
 KERNELS = ("gs_census_kernel", "gs_round_kernel", "gs_keys_kernel", "gs_color_ptr_kernel", "gs_color_kernel")

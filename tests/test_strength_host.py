@@ -19,7 +19,7 @@ from test_agg_host import cases as agg_cases
 from test_agg_host import TAGS as AGG_TAGS
 from test_agg_host import grid5_matrix, grid5_pairs, host_csr_aggregate
 from test_coo_host import LONG_RUN, SHARED, _FakeTensor, _f, _i, coo_sum_model
-from test_gs_host import csr_from_pattern, row_sum
+from test_gs_host import HELPERS, csr_from_pattern, row_sum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -76,7 +76,7 @@ STRENGTH_SIZE_RULES = [
      [VALUES, CAPTURE], "the filtered matrix (bits copied) against the smoother (omega = 2/3, 1.0, -0.5)"),
     ("a zero diag", CSRC + "k_strength.hip", r"if \(d == 0\.0\) return on_diag \? 1\.0 : 0\.0;",
      [VALUES], "identity rows: the 0.0 and -0.0 diagonals of the special values, the rows without a diagonal"),
-    ("kStrengthAlign", CSRC + "strength.cpp", r"constexpr size_t kStrengthAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [MODEL], "workspace parts are padded to 256 B (row and entry counts that are no multiple of 64: most cases)"),
     ("no rows", CSRC + "strength.cpp", r"if \(m == 0\) \{",
      [MODEL], "m == 0: nothing is read, written or allocated"),
@@ -84,8 +84,10 @@ STRENGTH_SIZE_RULES = [
      [VALUES], "nothing to launch"),
     ("no entries", CSRC + "k_strength.hip", r"if \(nnz <= 0\) return;",
      [MODEL, VALUES], "one_empty: a row without entries: the scatter and the values pass are not launched, diag is +0.0"),
-    ("int32 block arithmetic", CSRC + "strength.cpp", r"bool strength_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      [CONTRACT, VALUES_CONTRACT], "m or nnz beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
+    ("the census is shared", CSRC + "strength.cpp", r"pattern_census\(st, kEntry, ",
+     [CONTRACT, MODEL], "the refusals and their text are entry_helpers.hpp's, the same for the four entries; the count of rows without a diagonal comes back from it"),
 ]
 
 
@@ -104,7 +106,7 @@ def test_strength_size_rules_name_their_tests():
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             found += 1
             assert k in registered, f"{f}: constant {k} is not in STRENGTH_SIZE_RULES"
-    assert found == 8
+    assert found == 7
     header = open(os.path.join(ROOT, CSRC, "strength.hpp")).read()
     assert f"constexpr int kStrengthRankTile = {RANK_TILE};" in header and f"constexpr int kStrengthLumpPerLane = {LUMP_PER_LANE};" in header
     assert f"constexpr int kStrengthPerLane = {PER_LANE};" in header and LONG_RUN == 64
@@ -298,15 +300,16 @@ def test_strength_entries_keep_no_state():
     assert "plan_work_allowed(" in code.split("const auto leave = ")[0]  # (a capture is refused before anything is enqueued or allocated)
     assert "hipMalloc(" not in code.split("const auto leave = ")[0]
     after = code.split("const auto leave = ")[1].split("};", 1)[1].split("\n}\n")[0]  # (to the end of the routine that allocates)
-    launches = ("launch_gs_census", "launch_strength_sd", "launch_strength_flags", "launch_coo_scan", "launch_strength_ptrs", "launch_strength_scatter")
+    launches = ("pattern_census", "launch_strength_sd", "launch_strength_flags", "launch_coo_scan", "launch_strength_ptrs", "launch_strength_scatter")
     for launch in launches:
         assert launch in after, launch
     body = after.split("hipMalloc(")[1]
     assert [body.index(s + "(st, ") for s in launches] == sorted(body.index(s + "(st, ") for s in launches)  # the passes in the documented order
-    assert body.index("nothing was written") < body.index("launch_strength_sd(")  # the census is judged before anything is written
+    assert body.index("pattern_census(") < body.index("launch_strength_sd(")  # the census is judged before anything is written
+    assert 'pattern_census(st, kEntry, m, nnz, d_rowptr, d_colindex, d_slots, "filter A + A^T instead", ' in body
     bare = [ln.strip() for ln in after.splitlines() if re.search(r"\breturn\b(?! leave\()", ln)]
     # (the one way out that may skip leave(): the scratch query before the allocation)
-    assert bare == ['return strength_error(kEntry, kErrHip, "scan workspace query failed");'], bare
+    assert bare == ['return entry_error(kEntry, kErrHip, "scan workspace query failed");'], bare
     tail = after.split("launch_strength_scatter")[1]
     assert tail.index("*h_nnz_s = nnz_s;") < tail.index("*h_no_diag = ") < tail.index("return leave(kOk);")  # (written last, once everything else has run)
     assert "while (" not in code and "for (;;)" not in code  # no host loop that waits on the device
