@@ -14,6 +14,8 @@
 #ifndef SPMV_ACC_C_ABI_H
 #define SPMV_ACC_C_ABI_H
 
+#include <stddef.h> /* size_t (spmv_acc_cg_partials) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -669,6 +671,79 @@ int spmv_acc_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d
  * As measured (the same tool and file): 0.009 ms at 64, 256 and 1024 rows alike, plain or replayed from a graph (0.010 ms) -- one launch --,
  * 2.3 to 2.7 x torch's device copy of as many bytes, which is one launch as well (0.004 ms).  Larger inverses were not measured. */
 int spmv_acc_dense_apply(int m, const double *d_inv, const double *d_b, double *d_x);
+
+/* ---- conjugate-gradient vector passes, 1: the size of the partials buffer (new; host arithmetic) ------------------------------------------------
+ * replaces: nothing in the reference.  *h_count = the doubles the caller's d_partials must hold for vectors of n entries: 3 * ceil(n / 1024),
+ * three dot products' worth of one partial per 1024 terms (0 for n == 0).  Touches no device.
+ * COST: none.  CHECKS: a negative n, a null h_count: SPMV_ACC_ERR_BAD_ARGUMENT; n beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.
+ * CANNOT CHECK: that the buffer handed to the other three entries is that large. */
+int spmv_acc_cg_partials(int n, size_t *h_count);
+
+/* ---- conjugate-gradient vector passes, 2: the start (new; launch-only) ---------------------------------------------------------------------------
+ * replaces: nothing in the reference.  The three entries below are what preconditioned conjugate gradients need beside the SpMV q = A p and
+ * the preconditioner z = M r, which stay the caller's calls: every dot product, every scalar that depends on one, and every vector update
+ * stay on the device, so that iterations can be enqueued in batches without a host read.  The sequence for A x = b, A symmetric positive
+ * definite, M symmetric positive definite:
+ *     r = b - A x;  z = M r;  spmv_acc_cg_start;
+ *     repeat:  q = A p;  spmv_acc_cg_update;  z = M r;  spmv_acc_cg_direction;        (read d_state now and then: status != 0 ends the solve)
+ * The caller owns every array: the vectors (n doubles each), d_partials (spmv_acc_cg_partials doubles), the state block d_state (9 words of
+ * 8 bytes) and the optional history d_hist (hist_cap doubles; hist_cap == 0: none, d_hist may be NULL).
+ * THE DOT PRODUCT IS A PURE FUNCTION OF ITS TWO ARRAYS, bit for bit -- not of the grid, not of timing; no atomic, no kernel waits on another
+ * workgroup: term i = fl(u[i] * v[i]) (no fused multiply-add); partial c = the sum of the terms [1024 c, min(n, 1024 (c + 1))) by the 64 lanes
+ * of one wavefront in the order of spmv_acc_csr_gs_sweep with G = 64 (lane l the terms l, l + 64, ... in order from its first, a lane without
+ * a term holds +0.0; the 64 sums as a balanced tree over neighbouring lanes); the dot = the partials added the same way by the 256 lanes of
+ * ONE workgroup in a launch of its own (lane l the partials l, l + 256, ...; then the balanced tree over neighbouring lanes).  n == 0: +0.0.
+ * THE STATE BLOCK, written only by those finish workgroups, with ordinary stores (integer words are unsigned 64-bit, the others doubles):
+ *   [0] status: 0 running, 1 converged (rr <= tol2), 2 breakdown with p.q not finite or <= 0, 3 breakdown with r.z not finite or < 0
+ *   [1] iterations done   [2] bb = b.b   [3] rr = r.r   [4] rz = r.z   [5] pq = p.q   [6] alpha = rz / pq   [7] beta = rz_new / rz
+ *   [8] tol2 = fl(fl(rtol * rtol) * bb): rtol is squared first.  Both quotients are IEEE divisions.
+ * THIS ENTRY: the caller has computed r = b - A x and z = M r (d_z == d_r: no preconditioner).  Launch 1, one pass: the partials of b.b, r.r
+ * and r.z off the same loads, and p = z.  Launch 2, the finish: bb, rr, rz, tol2; iterations = 0; pq = alpha = beta = +0.0; hist[0] = rr;
+ * status = 3 if rz is not finite, else 1 if rr <= tol2 (b = 0, or an exact x0: no iteration is needed), else 3 if rz <= 0, else 0.
+ * Two launches on the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy, no host read, no plan; may be
+ * captured into a hipGraph.  n == 0 launches the finish alone (status 1).  CHECKS, on the host, nothing launched: a negative n or hist_cap,
+ * null pointers where data is needed, an rtol that is not finite or < 0, d_p, d_partials, d_state or d_hist overlapping each other or d_b,
+ * d_r or d_z (the single allowed alias is d_z == d_r): SPMV_ACC_ERR_BAD_ARGUMENT; n beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  Returns 0
+ * or an spmv_acc_error code.  CANNOT CHECK: that r and z are what the caller says, that A and M are symmetric positive definite (a breakdown
+ * status is the only sign), or that the buffers are as large as stated.
+ * COST: the pass reads 3 n doubles (2 n with d_z == d_r) and writes n; the finish reads 3 n / 1024.  As measured (MI355X, tools/cg_bench.py,
+ * profiles/cg_bench.md; 4.0 M rows, vectors warm in the Infinity Cache): 0.027 ms, 1.4 x torch's device copy of as many bytes. */
+int spmv_acc_cg_start(int n, double rtol, const double *d_b, const double *d_r, const double *d_z, double *d_p, double *d_partials,
+                      unsigned long long *d_state, double *d_hist, int hist_cap);
+
+/* ---- conjugate-gradient vector passes, 3: the update of x and r (new; the per-iteration hot path) -----------------------------------------------
+ * replaces: nothing in the reference.  The caller has computed q = A p.  Four launches: (1) the partials of p.q; (2) the finish: pq, and
+ * alpha = rz / pq if pq is finite and > 0, else status = 2; (3) the fused pass x[i] = x[i] + fl(alpha * p[i]), r[i] = r[i] - fl(alpha * q[i])
+ * and the partials of the new r.r, every product and sum rounded on its own; (4) the finish: rr, iterations += 1, hist[iterations] = rr while
+ * iterations < hist_cap, status = 1 if rr <= tol2.
+ * FROZEN MEANS FROZEN: every kernel of this entry and of spmv_acc_cg_direction reads the status first and, when it is not 0, returns before it
+ * writes anything: x, r, p, z, the partials, the state and the history keep their bits.  Iterations enqueued past the end of a solve change
+ * nothing, and the solution's bits do not depend on how often the host reads the state.
+ * On the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy, no host read, no plan; may be captured.
+ * CHECKS, on the host, nothing launched: a negative n or hist_cap, null pointers where data is needed, d_x, d_r, d_partials, d_state or d_hist
+ * overlapping each other or d_p or d_q: SPMV_ACC_ERR_BAD_ARGUMENT; n beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  Returns 0 or an
+ * spmv_acc_error code.  CANNOT CHECK: that q is A p, or that d_state and d_partials are those of the spmv_acc_cg_start of this solve.
+ * COST: 4 reads + 2 writes + 2 reads of n doubles (p, q; p, q, x, r, and x, r back), two finishes of n / 1024 doubles.  As measured (the
+ * same tool and file; 4.0 M rows, cache-warm): 0.047 ms for the four launches, 1.3 x a device copy of those bytes (1.6 x at 3.4 M rows). */
+int spmv_acc_cg_update(int n, const double *d_p, const double *d_q, double *d_x, double *d_r, double *d_partials, unsigned long long *d_state,
+                       double *d_hist, int hist_cap);
+
+/* ---- conjugate-gradient vector passes, 4: the new direction (new; the per-iteration hot path) ----------------------------------------------------
+ * replaces: nothing in the reference.  Three launches: (1) with d_dinv non-NULL the pass first writes z[i] = fl(dinv[i] * r[i]) -- the Jacobi
+ * preconditioner fused, no sweep of its own over r -- and takes the partials of r.z from it; with d_dinv == NULL it reads the caller's z = M r
+ * (d_z == d_r: no preconditioner); (2) the finish: rz_new; if it is finite and >= 0, beta = rz_new / rz and rz = rz_new, else status = 3 and
+ * both are kept; (3) p[i] = z[i] + fl(beta * p[i]).  Frozen as spmv_acc_cg_update is: with a status other than 0 nothing is written.
+ * THE ONE CALL THAT FINDS STATUS 3 has, with d_dinv, already written z = dinv r in its launch 1 (and the partials of r.z): that z is left as
+ * written, p is kept.  Likewise the update that finds status 2 has written the partials of p.q, and x and r are kept.
+ * On the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy, no host read, no plan; may be captured.
+ * CHECKS, on the host, nothing launched: a negative n, null pointers where data is needed, d_p, d_partials or d_state overlapping each other
+ * or d_r or d_z, and with d_dinv also d_z overlapping d_r, d_dinv or any of them (d_z == d_r is allowed only without d_dinv):
+ * SPMV_ACC_ERR_BAD_ARGUMENT; n beyond INT_MAX - 2^16: SPMV_ACC_ERR_TOO_LARGE.  Returns 0 or an spmv_acc_error code.  CANNOT CHECK: that z is
+ * M r for a symmetric positive definite M -- a V-cycle is one only from a zero start with symmetric sweeps --, or that dinv is positive.
+ * COST: 2 reads (3 and a write with d_dinv), then 2 reads + 1 write of n doubles, one finish.  As measured (the same tool and file; 4.0 M
+ * rows, cache-warm): 0.029 ms, with d_dinv 0.034 ms: 1.3 and 1.1 x a device copy of those bytes. */
+int spmv_acc_cg_direction(int n, const double *d_r, double *d_z, const double *d_dinv, double *d_p, double *d_partials,
+                          unsigned long long *d_state);
 
 /* ---- row sub-ranges of one matrix as consecutive launches over two streams (new) ------------------------------------------
  * replaces: nothing in the reference (one kernel per SpMV on the NULL stream).  The compute side of the pipelined row-sharded step

@@ -50,6 +50,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_aggregate", "spmv_acc_csr_tentative_values",
     "spmv_acc_csr_strength", "spmv_acc_csr_strength_values",
     "spmv_acc_csr_dense_inverse", "spmv_acc_dense_apply",
+    "spmv_acc_cg_partials", "spmv_acc_cg_start", "spmv_acc_cg_update", "spmv_acc_cg_direction",
 )
 
 _lib = None
@@ -186,6 +187,14 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_dense_inverse.restype = ci
     lib.spmv_acc_dense_apply.argtypes = [ci, vp, vp, vp]
     lib.spmv_acc_dense_apply.restype = ci
+    lib.spmv_acc_cg_partials.argtypes = [ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.spmv_acc_cg_partials.restype = ci
+    lib.spmv_acc_cg_start.argtypes = [ci, cd, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.spmv_acc_cg_start.restype = ci
+    lib.spmv_acc_cg_update.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.spmv_acc_cg_update.restype = ci
+    lib.spmv_acc_cg_direction.argtypes = [ci, vp, vp, vp, vp, vp, vp]
+    lib.spmv_acc_cg_direction.restype = ci
     if path is None:
         _lib = lib
     return lib
@@ -1055,6 +1064,97 @@ def dense_apply(m: int, inv, b, x) -> None:
         raise SpmvAccError(f"dense_apply failed ({rc})")
 
 
+CG_STATE = 9  # kCgState (spmv_acc_amd/csrc/cg.hpp): the 8-byte words of the state block
+CG_STATUS = ("running", "converged", "breakdown: p.q is not finite or <= 0", "breakdown: r.z is not finite or < 0")  # state word 0
+# the words of the state block, in order (include/spmv_acc.h): the first two are integers, the others doubles
+CG_WORDS = ("status", "iterations", "bb", "rr", "rz", "pq", "alpha", "beta", "tol2")
+
+
+def cg_partials(n: int) -> int:
+    """The doubles the partials buffer of cg_start / cg_update / cg_direction must hold for vectors of n entries (spmv_acc_cg_partials)."""
+    lib = load_library()
+    count = ctypes.c_size_t(0)
+    rc = lib.spmv_acc_cg_partials(n, ctypes.byref(count))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"cg_partials failed ({rc})")
+    return int(count.value)
+
+
+def _cg_args(lib, n, partials, state, hist, **vectors):
+    """The checks the three CG wrappers share: n fp64 entries per vector, the partials buffer of cg_partials(n), the state block as CG_STATE
+    int64 words, the optional history.  Returns hist_cap."""
+    if n < 0:
+        raise SpmvAccError(f"negative n ({n})")
+    _require_tensors(partials=partials, state=state, **vectors)
+    for name, t in vectors.items():
+        if int(t.numel()) != n:
+            raise SpmvAccError(f"{name} holds {int(t.numel())} elements, a vector of the {n} rows must hold as many")
+    if str(state.dtype) != "torch.int64" or int(state.numel()) != CG_STATE:
+        raise SpmvAccError(f"state: {int(state.numel())} elements of {state.dtype}, the state block is {CG_STATE} torch.int64 words")
+    if not state.is_cuda:
+        raise SpmvAccError("state: device pointers required, tensor is not on the GPU (no CPU fallback)")
+    if not state.is_contiguous():
+        raise SpmvAccError("state: tensor is not contiguous")
+    named = {name: (t, "f64", n) for name, t in vectors.items()}
+    named["partials"] = (partials, "f64", cg_partials(n))
+    hist_cap = 0
+    if hist is not None:
+        _require_tensors(hist=hist)
+        hist_cap = int(hist.numel())
+        named["hist"] = (hist, "f64", 0)
+    _require(lib, **named)
+    if state.device != partials.device:
+        raise SpmvAccError(f"state: on {state.device}, other arguments on {partials.device}")
+    return hist_cap
+
+
+def cg_start(n: int, rtol: float, b, r, z, p, partials, state, hist=None) -> None:
+    """The start of a conjugate-gradient solve (spmv_acc_cg_start, async on torch's current stream, capturable, two launches): the caller has
+    computed r = b - A x and z = M r (z is r: no preconditioner).  One pass takes b.b, r.r and r.z and writes p = z; one finish workgroup
+    sets the state block: iterations 0, tol2 = (rtol * rtol) * b.b, status 1 at once if r.r <= tol2, 3 if r.z is not finite or <= 0.
+    partials: cg_partials(n) fp64 entries; state: CG_STATE int64 words (CG_WORDS; view(torch.float64) reads the doubles); hist: optional fp64
+    tensor, hist[k] receives r.r of iteration k while k < len(hist).  Every dot product is bit for bit a pure function of its two arrays."""
+    lib = load_library()
+    if not (isinstance(rtol, (int, float)) and math.isfinite(rtol) and rtol >= 0.0):
+        raise SpmvAccError(f"rtol = {rtol}: a finite tolerance >= 0 is required")
+    hist_cap = _cg_args(lib, n, partials, state, hist, b=b, r=r, z=z, p=p)
+    rc = lib.spmv_acc_cg_start(n, float(rtol), _ptr(b) if n else 0, _ptr(r) if n else 0, _ptr(z) if n else 0, _ptr(p) if n else 0,
+                               _ptr(partials) if n else 0, _ptr(state), _ptr(hist) if hist_cap else 0, hist_cap)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"cg_start failed ({rc})")
+
+
+def cg_update(n: int, p, q, x, r, partials, state, hist=None) -> None:
+    """x += alpha p, r -= alpha q with alpha = r.z / p.q computed on the device (spmv_acc_cg_update, async, capturable, four launches); the
+    caller has computed q = A p.  Status 2 if p.q is not finite or <= 0; then r.r, the history, iterations + 1, and status 1 if r.r <= tol2.
+    With a status other than 0 nothing at all is written: iterations enqueued past the end of a solve change no bit."""
+    lib = load_library()
+    hist_cap = _cg_args(lib, n, partials, state, hist, p=p, q=q, x=x, r=r)
+    rc = lib.spmv_acc_cg_update(n, _ptr(p) if n else 0, _ptr(q) if n else 0, _ptr(x) if n else 0, _ptr(r) if n else 0, _ptr(partials) if n else 0,
+                                _ptr(state), _ptr(hist) if hist_cap else 0, hist_cap)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"cg_update failed ({rc})")
+
+
+def cg_direction(n: int, r, z, p, partials, state, dinv=None) -> None:
+    """p = z + beta p with beta = r.z_new / r.z computed on the device (spmv_acc_cg_direction, async, capturable, three launches).  dinv (an
+    fp64 tensor of n entries): z = dinv * r is written first, the Jacobi preconditioner fused; None: z is the caller's z = M r (z is r: no
+    preconditioner).  Status 3 if the new r.z is not finite or < 0.  With a status other than 0 nothing at all is written."""
+    lib = load_library()
+    vectors = dict(r=r, z=z, p=p)
+    if dinv is not None:
+        vectors["dinv"] = dinv
+    _cg_args(lib, n, partials, state, None, **vectors)
+    rc = lib.spmv_acc_cg_direction(n, _ptr(r) if n else 0, _ptr(z) if n else 0, _ptr(dinv) if dinv is not None and n else 0, _ptr(p) if n else 0,
+                                   _ptr(partials) if n else 0, _ptr(state))
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"cg_direction failed ({rc})")
+
+
 def prepare(m: int, n: int, nnz: int, rowptr, colindex, value, x, strategy=None, h_rowptr=None, beta: float = 1.0) -> float:
     """Build the plan of ``strategy`` for this matrix (structural passes + per-matrix timings) without touching any y, for the
     beta class the caller will run in (beta == 0 / beta != 0).  Returns the device milliseconds it took."""
@@ -1283,3 +1383,4 @@ def get_strategy() -> str:
 
 
 from .amg import AmgHierarchy, amg_cycle, amg_setup  # noqa: E402  (the hierarchy and the V-cycle, composed from the entries above)
+from .cg import CgResult, jacobi_inverse, pcg  # noqa: E402  (preconditioned conjugate gradients, composed from the entries above)

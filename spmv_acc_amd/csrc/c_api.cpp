@@ -22,6 +22,7 @@
 #include "agg.hpp"
 #include "strength.hpp"
 #include "dense.hpp"
+#include "cg.hpp"
 
 #include <string>
 #include <cstdint>
@@ -302,6 +303,23 @@ int spmv_acc_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d
 }
 
 int spmv_acc_dense_apply(int m, const double *d_inv, const double *d_b, double *d_x) { return run_dense_apply(m, d_inv, d_b, d_x); }
+
+int spmv_acc_cg_partials(int n, size_t *h_count) { return run_cg_partials(n, h_count); }
+
+int spmv_acc_cg_start(int n, double rtol, const double *d_b, const double *d_r, const double *d_z, double *d_p, double *d_partials,
+                      unsigned long long *d_state, double *d_hist, int hist_cap) {
+  return run_cg_start(n, rtol, d_b, d_r, d_z, d_p, d_partials, d_state, d_hist, hist_cap);
+}
+
+int spmv_acc_cg_update(int n, const double *d_p, const double *d_q, double *d_x, double *d_r, double *d_partials, unsigned long long *d_state,
+                       double *d_hist, int hist_cap) {
+  return run_cg_update(n, d_p, d_q, d_x, d_r, d_partials, d_state, d_hist, hist_cap);
+}
+
+int spmv_acc_cg_direction(int n, const double *d_r, double *d_z, const double *d_dinv, double *d_p, double *d_partials,
+                          unsigned long long *d_state) {
+  return run_cg_direction(n, d_r, d_z, d_dinv, d_p, d_partials, d_state);
+}
 
 int spmv_acc_csr_spmv_chunks(int strategy, double alpha, double beta, int n, int nchunks, const int *row_cuts, const int *nnz_ends,
                              const int *d_rowptr, const int *d_colindex, const double *d_value, const double *dx,
