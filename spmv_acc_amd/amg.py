@@ -13,7 +13,7 @@ import math
 from collections import namedtuple
 
 from . import (DENSE_MAX_ROWS, SpmvAccError, csr_aggregate, csr_color, csr_dense_inverse, csr_gs_sweep, csr_smooth_prolongator, csr_spgemm,
-               csr_spmv, csr_strength, csr_tentative, csr_transpose, dense_apply, release_plans, _require_tensors)
+               csr_spmv, csr_strength, csr_tentative, csr_transpose, dense_apply, release_plans, _GS_DIRECTIONS, _require_tensors)
 
 # One non-coarsest level: A = (rowptr, colindex, value) of m rows; P (m x mc) and R = P^T (mc x m) likewise; the colouring of A (color_ptr a
 # host list); the work vectors r (m), bc and xc (mc each), zero-initialised; keep: every other array of the level's setup, kept alive.
@@ -105,6 +105,8 @@ def amg_cycle(h: AmgHierarchy, b, x, pre: int = 1, post: int = 1, direction="sym
         raise SpmvAccError("h: the AmgHierarchy of amg_setup is required")
     if int(pre) < 0 or int(post) < 0:
         raise SpmvAccError(f"negative sweeps ({pre}, {post})")
+    if direction not in _GS_DIRECTIONS:  # (here, not only in csr_gs_sweep: a hierarchy of one level never sweeps)
+        raise SpmvAccError(f"amg_cycle: direction {direction!r}: one of {tuple(_GS_DIRECTIONS)}")
     _require_tensors(b=b, x=x)
     _cycle(h, 0, b, x, int(pre), int(post), direction)
 

@@ -39,8 +39,9 @@ def pcg(m: int, rowptr, colindex, value, b, x, precond=None, rtol: float = 1e-8,
       None             no preconditioner;
       an fp64 tensor   of m entries on the GPU: the inverse diagonal (jacobi_inverse), applied inside cg_direction;
       an AmgHierarchy  of amg_setup whose finest level has m rows: z = 0, then one amg_cycle(h, r, z, pre, post, "symmetric").  THE ZERO START
-                       AND THE SYMMETRIC SWEEPS are what make the cycle a symmetric operator z = M r, which conjugate gradients need: a
-                       forward-only sweep or a warm start would give a preconditioner that is not symmetric, and a breakdown or a stall;
+                       AND THE SYMMETRIC SWEEPS, with pre == post (the caller's to keep), are what make the cycle a symmetric operator
+                       z = M r, which conjugate gradients need: a forward-only sweep, a warm start or pre != post would give a
+                       preconditioner that is not symmetric, and a breakdown or a stall;
       a callable       precond(r, z) writes z = M r for a symmetric positive definite M, on torch's current stream.
     The order of an iteration: q = A p (csr_spmv); cg_update; z = M r; cg_direction.  The host reads the state block -- one copy of 72 bytes --
     after every check_every iterations and at maxiter, never inside a batch; iterations enqueued past the end of the solve write nothing, so x
