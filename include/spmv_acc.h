@@ -494,6 +494,61 @@ int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_coli
                           int ncolors, const int *h_color_ptr, const int *d_color_rows,
                           double omega, int direction, const double *d_b, double *d_x);
 
+/* ---- damped Jacobi / l1-Jacobi, 1: the inverse diagonal (new; once per set of values) --------------------------------------------------------
+ * replaces: nothing in the reference.  d_dinv (m doubles) for spmv_acc_csr_jacobi_sweep, of a square m x m CSR, int32, rebased, rows ascending.
+ * kind 0 (Jacobi): dinv[i] = 1.0 / a_ii, a_ii the stored diagonal entry; +0.0 where row i stores none.  kind 1 (scaled l1): with
+ * g[i] = sqrt(|a_ii|) (correctly rounded, +0.0 without a stored diagonal; written to d_work, m doubles, which kind 0 does not use and may
+ * pass as NULL),  d_i = the sum over the row's stored entries of |a_ij| * fl(g[i] / g[j])  -- the quotient rounded first, then the product; a
+ * column outside [0, m) contributes +0.0 --,  dinv[i] = 1.0 / d_i; +0.0 where row i stores no diagonal.  A zero or missing diagonal elsewhere
+ * in the sum gives what IEEE gives (x / 0 = inf, 1 / inf = +0, 0 / 0 = NaN).  For a symmetric A with a positive diagonal D = diag(d_i) >= A,
+ * so I - omega D^-1 A contracts in the energy norm for every omega in (0, 2), and D scales as A does under A -> S A S: no damping factor has to
+ * be chosen, on a badly scaled matrix either.  BIT FOR BIT a pure function of the arrays: the terms are added in spmv_acc_csr_gs_sweep's order
+ * on consecutive rows (a lane group G per 64 consecutive rows, lane l the terms l, l + G, ... from its first, a balanced tree over
+ * neighbouring lanes; spmv_acc_amd/csrc/jacobi.hpp spells it out, tests/test_jacobi_host.py host_jacobi_diagonal restates it in numpy).
+ * One launch (kind 0) or two (kind 1) on the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy, no
+ * plan, no census; capturable.  rowptr extents are clamped to [0, nnz] and a column outside [0, m) is never turned into an address: crafted
+ * arrays cannot make it read or write outside the caller's arrays.  CHECKS, on the host, nothing launched: null pointers where data is needed,
+ * negative sizes, a kind other than 0 or 1, d_work overlapping d_dinv: SPMV_ACC_ERR_BAD_ARGUMENT; a size beyond INT_MAX - 2^16, or kind 1 with
+ * more than 2^29 rows: SPMV_ACC_ERR_TOO_LARGE.  THE ENTRY CANNOT CHECK that A is symmetric or its diagonal positive, which the bound D >= A
+ * rests on.  Returns 0 or an spmv_acc_error code.
+ * COST: kind 0 reads rowptr and a binary search's worth of each row; kind 1 the bytes of one SpMV and one division per non-zero.  As measured
+ * (MI355X, tools/jacobi_bench.py, profiles/jacobi_bench.md; this entry on preallocated d_dinv and d_work, nothing allocated in the timed
+ * region), beside a settled SpMV of the engine on the same matrix in the same process: the FEM-quads matrix (4.0 M rows, 9-point), kind 0
+ * 0.087 ms = 1.15 SpMVs (0.0760 ms each), kind 1 0.265 ms = 3.5; the 27-point grid (3.4 M rows), 0.241 ms = 1.2 SpMVs (0.1972 ms each) and
+ * 0.511 ms = 2.6.  Against the colouring it replaces in an AMG setup (32-73 SpMVs a level):
+ * a tenth or less. */
+int spmv_acc_csr_jacobi_diagonal(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
+                                 int kind, double *d_dinv, double *d_work);
+
+/* ---- damped Jacobi / l1-Jacobi, 2: one sweep, the residual, or both (new; the per-step hot path) ---------------------------------------------
+ * replaces: nothing in the reference.  ONE launch for all rows, out of place.  For every row i:  s = the sum of value * x_in[col] over ALL the
+ * row's stored entries, the diagonal included (a column outside [0, m) contributes +0.0),  t = b[i] - s,  w = omega * dinv[i];
+ * r_out[i] = t if d_r_out is not NULL;  x_out[i] = x_in[i] + w * t if d_x_out is not NULL.  d_x_out alone: a sweep.  d_r_out alone: the
+ * residual b - A x without a plan.  Both: the sweep and the residual it started from.  ZERO START, d_x_in == NULL: the matrix is not read,
+ * t = b[i], x_out[i] = w * b[i] -- the first sweep from x = 0.  d_dinv from spmv_acc_csr_jacobi_diagonal (or the caller's own).
+ * BIT FOR BIT a pure function of the arrays and omega: every product, the subtraction and the update's product and sum are rounded on their
+ * own (no fused multiply-add); a row's terms are added by a group of G lanes, lane l the terms l, l + G, ... in order from its first, the G
+ * partial sums as a balanced tree over neighbouring lanes; G (a power of two, 1 .. 64) is the smallest with 4 G >= the mean row length of the
+ * 64 consecutive rows that one workgroup owns (spmv_acc_amd/csrc/jacobi.hpp; tests/test_jacobi_host.py host_jacobi_sweep restates it).
+ * rowptr extents are clamped to [0, nnz]: crafted arrays cannot make it read or write outside the caller's arrays.
+ * One launch on the calling thread's library stream: asynchronous, no allocation, no synchronisation, no copy, no plan, no atomics; may be
+ * captured into a hipGraph.  CHECKS, on the host, nothing launched: null pointers where data is needed, both outputs NULL, negative sizes, an
+ * omega that is not finite, any overlap among d_x_out, d_r_out, d_x_in, d_b and d_dinv (in place the rows would race):
+ * SPMV_ACC_ERR_BAD_ARGUMENT; a size beyond INT_MAX - 2^16 or more than 2^29 rows (x_in is gathered through 32-bit byte offsets):
+ * SPMV_ACC_ERR_TOO_LARGE.  THE ENTRY CANNOT CHECK that the iteration converges: that needs a symmetric positive definite A and, for kind 0's
+ * diagonal, an omega below 2 / the largest eigenvalue of D^-1 A (2/3 is customary), which is the caller's to choose.  Returns 0 or an
+ * spmv_acc_error code.
+ * COST: the bytes of one SpMV (12 B per non-zero, rowptr, b, x_in) plus dinv and the outputs, in one launch.  As measured (MI355X,
+ * tools/jacobi_bench.py, profiles/jacobi_bench.md), beside a settled SpMV of the engine on the same matrix in the same process: the FEM-quads
+ * matrix, a sweep 0.190 ms = 2.5 SpMVs, the residual alone 0.176 ms = 2.3, the zero start 0.017 ms = 0.2; the 27-point grid, 0.308 ms = 1.6
+ * SpMVs, 0.292 ms = 1.5 and 0.017 ms = 0.1.  THE KERNEL IS SLOWER THAN THE ENGINE: csr_spmv with y_in plus one torch pass does the same sweep in
+ * 1.4 and 1.1 SpMVs.  What this entry buys is its contract -- no plan, no per-matrix timing, one documented order, the same bits from the
+ * first call on -- and one launch where a symmetric multicolour sweep is 18 to 36: an AMG cycle on it costs 10.4 and 5.9 SpMVs against 41.7
+ * and 39.8 on Gauss-Seidel, and AMG-PCG to 1e-8 takes 40 and 31 ms against 110 and 139 ms, in 1.6-1.7 times the iterations. */
+int spmv_acc_csr_jacobi_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
+                              const double *d_dinv, double omega, const double *d_b, const double *d_x_in,
+                              double *d_x_out, double *d_r_out);
+
 /* ---- aggregation coarsening, 1: distance-2 independent roots and their aggregates (new; analysis) ------------------------------------------
  * replaces: nothing in the reference.  The coarsening step of an aggregation algebraic-multigrid setup on the device: it groups the rows of a
  * square matrix into aggregates and returns them as the CSR structures of the tentative prolongator P (m x naggs, one entry per row) and of

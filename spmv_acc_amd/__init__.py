@@ -47,6 +47,7 @@ C_ABI_SYMBOLS = (
     "spmv_acc_csr_add", "spmv_acc_csr_add_values",
     "spmv_acc_csr_extract", "spmv_acc_csr_extract_values",
     "spmv_acc_csr_color", "spmv_acc_csr_gs_sweep",
+    "spmv_acc_csr_jacobi_diagonal", "spmv_acc_csr_jacobi_sweep",
     "spmv_acc_csr_aggregate", "spmv_acc_csr_tentative_values",
     "spmv_acc_csr_strength", "spmv_acc_csr_strength_values",
     "spmv_acc_csr_dense_inverse", "spmv_acc_dense_apply",
@@ -175,6 +176,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.spmv_acc_csr_color.restype = ci
     lib.spmv_acc_csr_gs_sweep.argtypes = [ci, ci, vp, vp, vp, ci, _c_int_p, vp, cd, ci, vp, vp]
     lib.spmv_acc_csr_gs_sweep.restype = ci
+    lib.spmv_acc_csr_jacobi_diagonal.argtypes = [ci, ci, vp, vp, vp, ci, vp, vp]
+    lib.spmv_acc_csr_jacobi_diagonal.restype = ci
+    lib.spmv_acc_csr_jacobi_sweep.argtypes = [ci, ci, vp, vp, vp, vp, cd, vp, vp, vp, vp]
+    lib.spmv_acc_csr_jacobi_sweep.restype = ci
     lib.spmv_acc_csr_aggregate.argtypes = [ci, ci, vp, vp, vp, vp, vp, _c_int_p]
     lib.spmv_acc_csr_aggregate.restype = ci
     lib.spmv_acc_csr_tentative_values.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -821,6 +826,66 @@ def csr_gs_sweep(m: int, rowptr, colindex, value, color_ptr, color_rows, b, x, o
         if rc != 0:
             _check(lib)
             raise SpmvAccError(f"csr_gs_sweep failed ({rc})")
+
+
+_JACOBI_KINDS = {"jacobi": 0, "l1": 1}
+
+
+def csr_jacobi_diagonal(m: int, rowptr, colindex, value, kind="l1"):
+    """The inverse diagonal csr_jacobi_sweep takes, of a square m x m CSR with ascending rows (spmv_acc_csr_jacobi_diagonal, async on torch's
+    current stream, capturable): returns dinv, fp64 on the GPU.  kind "jacobi": 1 / a_ii.  kind "l1": 1 / d_i with the scaled l1 diagonal
+    d_i = sum_j |a_ij| sqrt(|a_ii|) / sqrt(|a_jj|), which bounds a symmetric A with a positive diagonal from above (D >= A: the sweep
+    contracts in the energy norm for every omega in (0, 2)) and scales as A does under A -> S A S.  +0.0 where a row stores no diagonal.  The
+    work vector of kind "l1" (m doubles) is allocated here.  Bit for bit a pure function of the arrays.  len(colindex) must be rowptr[m]."""
+    import torch
+
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    if kind not in _JACOBI_KINDS:
+        raise SpmvAccError(f"kind {kind!r}: one of {tuple(_JACOBI_KINDS)}")
+    _require_tensors(rowptr=rowptr, colindex=colindex, value=value)
+    nnz = int(colindex.numel())
+    if int(value.numel()) > nnz:  # (fewer: the "elements" check below)
+        raise SpmvAccError(f"colindex holds {nnz} elements, value must hold as many")
+    _require(lib, rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0), value=(value, "f64", nnz))
+    dinv = torch.empty(m, dtype=torch.float64, device=rowptr.device)
+    work = torch.empty(m, dtype=torch.float64, device=rowptr.device) if kind == "l1" else None
+    rc = lib.spmv_acc_csr_jacobi_diagonal(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(value) if nnz else 0, _JACOBI_KINDS[kind],
+                                          _ptr(dinv) if m else 0, _ptr(work) if work is not None and m else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_jacobi_diagonal failed ({rc})")
+    return dinv
+
+
+def csr_jacobi_sweep(m: int, rowptr, colindex, value, dinv, b, x_in, x_out=None, r_out=None, omega: float = 1.0) -> None:
+    """One damped Jacobi sweep towards A x = b, out of place, in ONE launch (spmv_acc_csr_jacobi_sweep, async on torch's current stream,
+    capturable): with t = b - A x_in, r_out = t (if given) and x_out = x_in + omega * dinv * t (if given); at least one of the two.  x_in=None
+    is the zero start: the matrix is not read, t = b, x_out = omega * dinv * b.  dinv from csr_jacobi_diagonal.  Bit for bit a pure function of
+    the arrays and omega.  x_out, r_out, x_in, b and dinv must not overlap: ping-pong between two vectors."""
+    lib = load_library()
+    if m < 0:
+        raise SpmvAccError(f"negative shape ({m}, {m})")
+    if not (isinstance(omega, (int, float)) and math.isfinite(omega)):
+        raise SpmvAccError(f"omega = {omega}: a finite relaxation factor is required")
+    if x_out is None and r_out is None:
+        raise SpmvAccError("x_out and r_out are both None: nothing to write")
+    _require_tensors(rowptr=rowptr, colindex=colindex, value=value, dinv=dinv, b=b)
+    optional = {name: t for name, t in (("x_in", x_in), ("x_out", x_out), ("r_out", r_out)) if t is not None}
+    _require_tensors(**optional)
+    nnz = int(colindex.numel())
+    if int(value.numel()) > nnz:  # (fewer: the "elements" check below)
+        raise SpmvAccError(f"colindex holds {nnz} elements, value must hold as many")
+    named = dict(rowptr=(rowptr, "i32", m + 1), colindex=(colindex, "i32", 0), value=(value, "f64", nnz), dinv=(dinv, "f64", m), b=(b, "f64", m))
+    named.update({name: (t, "f64", m) for name, t in optional.items()})
+    _require(lib, **named)
+    rc = lib.spmv_acc_csr_jacobi_sweep(m, nnz, _ptr(rowptr), _ptr(colindex) if nnz else 0, _ptr(value) if nnz else 0, _ptr(dinv) if m else 0,
+                                       float(omega), _ptr(b) if m else 0, _ptr(x_in) if x_in is not None and m else 0,
+                                       _ptr(x_out) if x_out is not None and m else 0, _ptr(r_out) if r_out is not None and m else 0)
+    if rc != 0:
+        _check(lib)
+        raise SpmvAccError(f"csr_jacobi_sweep failed ({rc})")
 
 
 def csr_aggregate(m: int, rowptr, colindex):

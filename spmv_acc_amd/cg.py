@@ -41,7 +41,8 @@ def pcg(m: int, rowptr, colindex, value, b, x, precond=None, rtol: float = 1e-8,
       an AmgHierarchy  of amg_setup whose finest level has m rows: z = 0, then one amg_cycle(h, r, z, pre, post, "symmetric").  THE ZERO START
                        AND THE SYMMETRIC SWEEPS, with pre == post (the caller's to keep), are what make the cycle a symmetric operator
                        z = M r, which conjugate gradients need: a forward-only sweep, a warm start or pre != post would give a
-                       preconditioner that is not symmetric, and a breakdown or a stall;
+                       preconditioner that is not symmetric, and a breakdown or a stall.  A hierarchy of a Jacobi smoother
+                       (amg_setup(smoother=...)) is cycled with zero_start=True instead of z = 0; pre == post keeps M symmetric;
       a callable       precond(r, z) writes z = M r for a symmetric positive definite M, on torch's current stream.
     The order of an iteration: q = A p (csr_spmv); cg_update; z = M r; cg_direction.  The host reads the state block -- one copy of 72 bytes --
     after every check_every iterations and at maxiter, never inside a batch; iterations enqueued past the end of the solve write nothing, so x
@@ -81,8 +82,11 @@ def pcg(m: int, rowptr, colindex, value, b, x, precond=None, rtol: float = 1e-8,
 
     def apply_precond():
         if isinstance(precond, AmgHierarchy):
-            z.zero_()
-            amg_cycle(precond, r, z, int(pre), int(post), "symmetric")
+            if precond.smoother == "gs":
+                z.zero_()
+                amg_cycle(precond, r, z, int(pre), int(post), "symmetric")
+            else:  # a Jacobi hierarchy starts from zero itself and never reads what z holds
+                amg_cycle(precond, r, z, int(pre), int(post), "symmetric", zero_start=True)
         elif dinv is None and precond is not None:
             precond(r, z)
 

@@ -23,6 +23,7 @@
 #include "strength.hpp"
 #include "dense.hpp"
 #include "cg.hpp"
+#include "jacobi.hpp"
 
 #include <string>
 #include <cstdint>
@@ -277,6 +278,16 @@ int spmv_acc_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colinde
 int spmv_acc_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, int ncolors, const int *h_color_ptr,
                           const int *d_color_rows, double omega, int direction, const double *d_b, double *d_x) {
   return run_csr_gs_sweep(m, nnz, d_rowptr, d_colindex, d_value, ncolors, h_color_ptr, d_color_rows, omega, direction, d_b, d_x);
+}
+
+int spmv_acc_csr_jacobi_diagonal(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, int kind, double *d_dinv,
+                                 double *d_work) {
+  return run_csr_jacobi_diagonal(m, nnz, d_rowptr, d_colindex, d_value, kind, d_dinv, d_work);
+}
+
+int spmv_acc_csr_jacobi_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, const double *d_dinv, double omega,
+                              const double *d_b, const double *d_x_in, double *d_x_out, double *d_r_out) {
+  return run_csr_jacobi_sweep(m, nnz, d_rowptr, d_colindex, d_value, d_dinv, omega, d_b, d_x_in, d_x_out, d_r_out);
 }
 
 int spmv_acc_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_colindex, int *d_agg, int *d_agg_rows, int *d_agg_ptr, int *h_naggs) {
