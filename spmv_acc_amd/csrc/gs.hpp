@@ -32,9 +32,10 @@
 //       [0, m) --,   g = (b[i] - s) / a_ii,   x[i] = g if omega == 1.0 else x[i] + omega * (g - x[i]).
 // Contraction is off: every product, the subtraction, the division and the relaxation are rounded on their own.  A row without a stored
 // diagonal is left untouched, a row index outside [0, m) is skipped, a zero diagonal gives what IEEE division gives.
-// THE SUMMATION ORDER is that of coo.hpp, generalised to a lane group of width G (a power of two, 1 .. 64): lane l adds the terms l, l + G,
-// l + 2 G, ... of the row in that order, starting from its first (a lane without a term holds +0.0); the G partial sums are combined as a
-// balanced binary tree over neighbouring lanes (q[i] = p[2 i] + p[2 i + 1], then the same on q, ... down to one).
+// THE SUMMATION ORDER (its device code: row_sweep.hpp, which the Jacobi kernels run too) is that of coo.hpp, generalised to a lane group of
+// width G (a power of two, 1 .. 64): lane l adds the terms l, l + G, l + 2 G, ... of the row in that order, starting from its first (a lane
+// without a term holds +0.0); the G partial sums are combined as a balanced binary tree over neighbouring lanes (q[i] = p[2 i] + p[2 i + 1],
+// then the same on q, ... down to one).
 // G IS CHOSEN ON THE DEVICE, per chunk: a workgroup owns kGsChunkRows consecutive positions of the colour, counted from the colour's first
 // (the last chunk of a colour is shorter), adds up the (clamped) lengths of its rows and takes the smallest G with
 // G * kGsTermsPerLane * rows of the chunk >= that sum, at most 64.  The entry is launch-only, so the host never learns a row length; the

@@ -29,11 +29,10 @@
 // The sweep is out of place because Jacobi in place would race: x_out, r_out, x_in, b and dinv must not overlap each other.
 // SIZE LIMIT: at most kJacobiMaxRows = 2^29 rows for the sweep and the scaled l1 diagonal, whose kernels gather through 32-bit byte offsets
 // (8 * column < 2^32); more rows are refused with SPMV_ACC_ERR_TOO_LARGE before any launch.
-// THE SUMMATION ORDER is the Gauss-Seidel sweep's (gs.hpp) on consecutive rows: a workgroup owns kJacobiTile = kGsChunkRows consecutive rows
-// (the last chunk is shorter), adds up their clamped lengths and takes the smallest lane group G (a power of two, 1 .. 64) with
-// G * kGsTermsPerLane * rows of the chunk >= that sum; lane l adds the terms l, l + G, ... of the row in that order, starting from its first
-// (a lane without a term holds +0.0); the G partial sums are combined as a balanced binary tree over neighbouring lanes.  The scaled l1
-// diagonal is summed in the same order.  Every result is therefore a pure function of the arrays -- not of the grid, not of timing.
+// THE SUMMATION ORDER is the Gauss-Seidel sweep's, defined in gs.hpp (THE SUMMATION ORDER, G IS CHOSEN ON THE DEVICE) and run by the same device
+// code (row_sweep.hpp), with the rows [0, m) as the one colour and no color_rows: the chunks are kJacobiTile = kGsChunkRows consecutive rows.
+// The scaled l1 diagonal is summed in the same order.  Every result is therefore a pure function of the arrays -- not of the grid, not of
+// timing.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

@@ -13,16 +13,14 @@
 //    -1) to the other buffer; the rows still uncoloured are counted per wavefront.
 // 3. Keys (gs_keys_kernel, 8) and colour pointer (gs_color_ptr_kernel, 9): the colour as the sort key of the library's stable radix sort, whose
 //    order IS color_rows; color_ptr[c] by a binary search in the sorted keys.
-// 4. Sweep of one colour (gs_color_kernel, 48; the per-step hot path): a workgroup owns 64 consecutive rows of the colour; each of its wavefronts reads
-//    their extents one per lane, chooses the lane group G from their mean length (gs.hpp) and takes every fourth pass of 64 / G rows: per row, G lanes stream colindex
-//    and value and gather x -- a step loads up to four terms per lane, all of them before any arithmetic (on a mesh a row is one step: straight-line
-//    selects), and adds them in order --; the G partial sums go through the DPP butterfly
-//    (neighbouring lanes first: the balanced tree of gs.hpp).  The diagonal is found in passing (a ballot names its lane).  Contraction is off.
+// 4. Sweep of one colour (gs_color_kernel, 47; the per-step hot path): the policy ColorRows on row_sweep.hpp's lane_group_rows, the one row-sum
+//    body that the Jacobi kernels run too (chunks of 64 positions of the colour, the lane group G, the passes, the four terms a step, the
+//    butterfly and the diagonal's ballot are described there).  What is this kernel's own: the row of a position comes through color_rows, the
+//    diagonal's term is +0.0, lane 0 of the group divides by the diagonal and relaxes.  Contraction is off.
 //    colindex and value are read with the default cache policy: the backward half of a symmetric sweep starts on the colours the forward half
 //    read last (supposed to help while they are still cached; the two policies were not timed against each other).  x is gathered through
 //    32-bit byte offsets (device_utils.hpp gather_u32; m <= kGsMaxRows): with 64-bit gather addresses the kernel takes 65 VGPRs, 7 waves per SIMD.
-#include "gs.hpp"
-#include "structure_passes.hpp"
+#include "row_sweep.hpp"
 
 namespace spmv_acc {
 namespace {
@@ -131,105 +129,42 @@ __global__ __launch_bounds__(kThreads) void gs_color_ptr_kernel(int m, const u64
     ptr[c] = first_at_least(sorted, 0, m, static_cast<u64>(c));
 }
 
-// the term of position p of row i (gs.hpp): +0.0 at the diagonal, which is noted, and for a column outside [0, m)
-struct GsTerm {
-  int c;
-  double v;
-};
-__device__ __forceinline__ GsTerm gs_load(const int *__restrict__ colindex, const double *__restrict__ value, int p) {
-  GsTerm t;
-  t.c = colindex[p];
-  t.v = value[p];
-  return t;
-}
-// (m <= kGsMaxRows: the byte offset of a column inside [0, m) fits 32 bits)
-__device__ __forceinline__ double gs_gather(const double *x, int m, int c) {
-  return static_cast<unsigned>(c) < static_cast<unsigned>(m) ? gather_u32(x, c) : 0.0;
-}
-__device__ __forceinline__ double gs_term(const GsTerm &t, double xc, int m, int i, bool *has, double *diag) {
+// What a row's lane group does in a colour's sweep (row_sweep.hpp names the members): the row comes through color_rows, the diagonal's term is
+// +0.0, and a row without a stored diagonal is left untouched.  x is read and written (different elements, by the colouring): not __restrict__.
+struct ColorRows {
+  const int *__restrict__ color_rows;
+  double omega;
+  const double *__restrict__ b;
+  double *x;
+  __device__ __forceinline__ const double *gathered() const { return x; }
+  __device__ __forceinline__ int row_at(long long pos) const {
+    return color_rows != nullptr ? load_stream(color_rows + pos) : static_cast<int>(pos);
+  }
+  __device__ __forceinline__ double begin(int) const { return 0.0; }
+  __device__ __forceinline__ double term(double v, double xc, double, bool on_diag) const {
 #pragma clang fp contract(off)
-  const bool on_diag = t.c == i;
-  *has = *has || on_diag;
-  *diag = on_diag ? t.v : *diag;
-  const double prod = t.v * xc;
-  return on_diag || static_cast<unsigned>(t.c) >= static_cast<unsigned>(m) ? 0.0 : prod;
-}
+    const double prod = v * xc;
+    return on_diag ? 0.0 : prod;
+  }
+  __device__ __forceinline__ void finish(int i, double s, bool has_diag, double a_ii) const {
+#pragma clang fp contract(off)
+    if (!has_diag) return;
+    const double gs = (b[i] - s) / a_ii;
+    if (omega == 1.0) {
+      x[i] = gs;
+    } else {
+      const double xi = x[i];
+      x[i] = xi + omega * (gs - xi);
+    }
+  }
+};
 
-// One workgroup per chunk of kGsTile = kGsChunkRows positions of the colour [first, last), blocks stride over the chunks beyond the grid.  Every
-// wavefront of the workgroup reads the chunk's extents and finds the same G; the chunk's G passes of 64 / G rows are dealt out to the four
-// wavefronts in turn (G = 1: one pass, three wavefronts leave at once), so a launch holds four times the wavefronts of one chunk per
-// wavefront and none walks more than G / 4 passes one after the other.  x is read and written (different elements, by the colouring): not
-// __restrict__.
 __global__ __launch_bounds__(kThreads) void gs_color_kernel(int m, int nnz, const int *__restrict__ rowptr, const int *__restrict__ colindex,
                                                             const double *__restrict__ value, int first, int last,
                                                             const int *__restrict__ color_rows, double omega, const double *__restrict__ b,
                                                             double *x) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const long long ntiles = (static_cast<long long>(last) - first + kGsTile - 1) / kGsTile;
-  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) { // (block-uniform)
-    const long long base = first + tile * kGsTile; // (< last; the workgroup's four wavefronts share the chunk and deal its passes out)
-    const int rows_here = last - base < kGsChunkRows ? static_cast<int>(last - base) : kGsChunkRows;
-    // lane r holds the row of position base + r: its index (-1: none, or outside [0, m)) and its clamped extent
-    int my_i = -1, my_lo = 0, my_hi = 0;
-    if (lane < rows_here) {
-      const int i = color_rows != nullptr ? load_stream(color_rows + base + lane) : static_cast<int>(base + lane);
-      if (static_cast<unsigned>(i) < static_cast<unsigned>(m)) {
-        my_i = i;
-        my_lo = row_extent(rowptr, nnz, i, &my_hi);
-      }
-    }
-    u64 total = static_cast<u64>(my_hi - my_lo);
-    for (int off = kWave / 2; off > 0; off >>= 1) total += __shfl_xor(total, off, kWave);
-    const u64 terms = static_cast<u64>(__builtin_amdgcn_readfirstlane(static_cast<int>(total >> 32))) << 32 |
-                      static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(total)));
-    int g = 1, log_g = 0; // the lane group (gs.hpp): the smallest G with G * kGsTermsPerLane * rows_here >= terms, at most 64
-    while (g < kWave && static_cast<u64>(g) * kGsTermsPerLane * rows_here < terms) {
-      g <<= 1;
-      ++log_g;
-    }
-    const int per_pass = kWave >> log_g; // rows per pass
-    const int slot = lane >> log_g;      // this lane's row of the pass
-    const int l = lane & (g - 1);        // ... and its place in the row's lane group
-    for (int done = wave * per_pass; done < rows_here; done += (kThreads / kWave) * per_pass) { // (wave-uniform)
-      const int k = done + slot; // (< 64: per_pass divides 64)
-      const int i = __shfl(my_i, k, kWave);
-      const int lo = __shfl(my_lo, k, kWave), hi = __shfl(my_hi, k, kWave);
-      bool has = false;
-      double diag = 0.0, part = 0.0;
-      bool opened = false; // the sum starts from the lane's first term, not from 0.0
-      for (int p = lo + l; p < hi; p += 4 * g) { // up to four terms a step (on a mesh: one step), every load issued before the arithmetic
-        const int p1 = p + g, p2 = p + 2 * g, p3 = p + 3 * g;
-        const bool live1 = p1 < hi, live2 = p2 < hi, live3 = p3 < hi; // (a position beyond the row reads p again and is not added)
-        const GsTerm t0 = gs_load(colindex, value, p), t1 = gs_load(colindex, value, live1 ? p1 : p);
-        const GsTerm t2 = gs_load(colindex, value, live2 ? p2 : p), t3 = gs_load(colindex, value, live3 ? p3 : p);
-        const double x0 = gs_gather(x, m, t0.c), x1 = gs_gather(x, m, t1.c), x2 = gs_gather(x, m, t2.c), x3 = gs_gather(x, m, t3.c);
-        const double w0 = gs_term(t0, x0, m, i, &has, &diag), w1 = gs_term(t1, x1, m, i, &has, &diag);
-        const double w2 = gs_term(t2, x2, m, i, &has, &diag), w3 = gs_term(t3, x3, m, i, &has, &diag);
-        part = opened ? part + w0 : w0;
-        opened = true;
-        part = live1 ? part + w1 : part;
-        part = live2 ? part + w2 : part;
-        part = live3 ? part + w3 : part;
-      }
-      const double s = group_sum_dyn(part, g);
-      // the diagonal: the first lane of the group that met it
-      u64 holders = __ballot(has) >> (slot << log_g);
-      if (g < kWave) holders &= (1ull << g) - 1;
-      const int owner = holders != 0 ? (slot << log_g) + (__ffsll(static_cast<long long>(holders)) - 1) : lane;
-      const double a_ii = __shfl(diag, owner, kWave);
-      if (l == 0 && i >= 0 && holders != 0) { // a row without a stored diagonal is left untouched
-        const double gs = (b[i] - s) / a_ii;
-        if (omega == 1.0) {
-          x[i] = gs;
-        } else {
-          const double xi = x[i];
-          x[i] = xi + omega * (gs - xi);
-        }
-      }
-    }
-  }
+  const ColorRows rows{color_rows, omega, b, x};
+  lane_group_rows(m, nnz, rowptr, colindex, value, first, last, rows);
 }
 
 } // namespace

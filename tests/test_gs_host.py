@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
 NEW_SOURCES = ("gs.hpp", "k_gs.hip", "gs.cpp")
 HELPERS = "entry_helpers.hpp"  # what the four entry files of the AMG chain share: the other features' tables name it too
+ROW_SWEEP = "row_sweep.hpp"  # the one row-sum body of gs_color_kernel and the two Jacobi kernels: test_jacobi_host.py's table names it too
 ENTRY_FILES = ("gs.cpp", "agg.cpp", "strength.cpp", "dense.cpp")
 COLOR = "test_color_is_the_host_model"
 SWEEP = "test_sweep_is_the_host_model"
@@ -50,11 +51,11 @@ GS_SIZE_RULES = [
     ("kGsTile", CSRC + "gs.hpp", r"constexpr int kGsTile = kGsChunkRows;",
      [SWEEP, STRIDE], "rows per workgroup: one chunk, its passes dealt out to the four wavefronts (G = 1: three leave at once; G = 64: 16 passes "
                       "each; path: colours of 11 workgroups; the stride test's largest colours: 400 and more)"),
-    ("the passes of a chunk", CSRC + "k_gs.hip", r"for \(int done = wave \* per_pass; done < rows_here; done \+= \(kThreads / kWave\) \* per_pass\) \{",
+    ("the passes of a chunk", CSRC + ROW_SWEEP, r"for \(int done = wave \* per_pass; done < rows_here; done \+= \(kThreads / kWave\) \* per_pass\) \{",
      [SWEEP], "a chunk of fewer rows than passes x rows per pass leaves wavefronts without a pass (k130, star's hub: chunks of one row)"),
     ("kGsTermsPerLane", CSRC + "gs.hpp", r"constexpr int kGsTermsPerLane = 4;",
      [SWEEP], "the lane group: G = 1 (path, star's leaves), 2 (grid7), 4 (fem), 8 (grid27), 16 (band25), 32 (band50), 64 (k130, star's hub)"),
-    ("the lane group's rule", CSRC + "k_gs.hip", r"while \(g < kWave && static_cast<u64>\(g\) \* kGsTermsPerLane \* rows_here < terms\) \{",
+    ("the lane group's rule", CSRC + ROW_SWEEP, r"while \(g < kWave && static_cast<u64>\(g\) \* kGsTermsPerLane \* rows_here < terms\) \{",
      [SWEEP], "the smallest G with G * 4 * rows of the chunk >= the chunk's terms, at most 64 (star's hub: 300 terms in a chunk of one row)"),
     ("kGsMaxRows", CSRC + "gs.hpp", r"constexpr int kGsMaxRows = 1 << 29;",
      [SWEEP_CONTRACT], "more rows than 32-bit gather offsets reach: SPMV_ACC_ERR_TOO_LARGE on the host"),
@@ -66,7 +67,7 @@ GS_SIZE_RULES = [
      [STRIDE, COLOR], "the census and every round take the shared census grid, one row per lane"),
     ("row loops of the census and the rounds", CSRC + "k_gs.hip", r"r < m; r \+= stride\) \{",
      [STRIDE], "one row per lane, striding (the stride test: 64 000 rows over 64 workgroups); the census: r <= m"),
-    ("tile loop of the sweep", CSRC + "k_gs.hip",
+    ("tile loop of the sweep", CSRC + ROW_SWEEP,
      r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\) \{ // \(block-uniform\)\n    const long long base = first \+ tile \* kGsTile",
      [STRIDE], "blocks stride over the tiles of a colour beyond the grid"),
     ("kMaxGridBlocks (grid striding)", CSRC + SHARED, r"const long long cap = max_grid_blocks\(\);",
@@ -77,7 +78,7 @@ GS_SIZE_RULES = [
      [COLOR, "test_color_cap_too_small"], "one colour per lane: min(cap_colors, m) + 1 entries (the wrapper's 1 024 exceed m on k130 and star)"),
     ("more colours than the caller's array", CSRC + "gs.cpp", r"if \(ncolors > cap_colors\)",
      ["test_color_cap_too_small"], "SPMV_ACC_ERR_TOO_LARGE with the count; the wrapper calls again"),
-    ("a row without a diagonal", CSRC + "k_gs.hip", r"if \(l == 0 && i >= 0 && holders != 0\) \{",
+    ("a row without a diagonal", CSRC + "k_gs.hip", r"if \(!has_diag\) return;",
      [SWEEP, SWEEP_CONTRACT], "left untouched (the cases with diagonals removed); a row index outside [0, m) is skipped"),
     ("omega == 1", CSRC + "k_gs.hip", r"if \(omega == 1\.0\) \{",
      [SWEEP], "x[i] = g without the relaxation's two roundings; else x + omega * (g - x)"),
@@ -112,8 +113,11 @@ def test_gs_size_rules_name_their_tests():
     header = open(os.path.join(ROOT, CSRC, "gs.hpp")).read()
     assert f"constexpr int kGsChunkRows = {CHUNK_ROWS};" in header and f"constexpr int kGsTermsPerLane = {TERMS_PER_LANE};" in header
     assert f"constexpr int kGsColorWindow = {WINDOW};" in header
-    kernels = open(os.path.join(ROOT, CSRC, "k_gs.hip")).read()
-    assert kernels.count("tile += gridDim.x") == 1 and kernels.count("+= stride)") == 4  # every loop over work is one of the registered forms
+    # every loop over work is one of the registered forms: the one tile loop stands in the shared body, which the sweep calls once
+    kernels, body = open(os.path.join(ROOT, CSRC, "k_gs.hip")).read(), open(os.path.join(ROOT, CSRC, ROW_SWEEP)).read()
+    assert body.count("tile += gridDim.x") == 1 and kernels.count("tile += gridDim.x") == 0 and kernels.count("+= stride)") == 4
+    assert "+= stride)" not in body and kernels.count("lane_group_rows(") == 1
+    assert kernels.count("lane_group_rows(m, nnz, rowptr, colindex, value, first, last, rows);") == 1
 
 
 PROTOTYPES = (
@@ -330,9 +334,36 @@ def test_entry_helpers_keep_no_state():
     assert HELPERS in open(os.path.join(ROOT, CSRC, "Makefile")).read()
 
 
+ROW_SWEEP_FUNCTIONS = ["row_term_load", "row_gather", "row_term", "lane_group_rows"]
+
+
+def test_row_sweep_keeps_no_state():
+    """What gs_color_kernel, jacobi_sweep_kernel and jacobi_l1_kernel share on the device is a fixed list of forced-inline functions: no atomic,
+    no LDS, no barrier and no constant of its own (the tile constants stay in gs.hpp); and the copies are gone from the two kernel files."""
+    src = open(os.path.join(ROOT, CSRC, ROW_SWEEP)).read()
+    code = re.sub(r"//[^\n]*", "", src)
+    for word in ("atomic", "__shared__", "__syncthreads", "constexpr", "__global__"):
+        assert word not in code, word
+    assert not re.search(r"\bstatic\b", code)
+    functions = re.findall(r"^(\w[\w ]*?)\b(\w+)\(", code, flags=re.M)
+    assert [name for _, name in functions] == ROW_SWEEP_FUNCTIONS, functions
+    assert all(kind.startswith("__device__ __forceinline__ ") for kind, _ in functions), functions
+    assert code.count("struct ") == 1 and "struct RowTerm {" in code  # the term record, defined once
+    assert '#include "gs.hpp"' in src and '#include "structure_passes.hpp"' in src and "namespace passes {" in src
+    for f in ("k_gs.hip", "k_jacobi.hip"):
+        kernels = open(os.path.join(ROOT, CSRC, f)).read()
+        assert '#include "' + ROW_SWEEP + '"' in kernels, f
+        for gone in ("GsTerm", "JacobiTerm", "gs_load", "jacobi_load", "gs_gather", "jacobi_gather", "gs_term(", "jacobi_term(", "jacobi_rows", "bool opened",
+                     "readfirstlane"):
+            assert gone not in kernels, (f, gone)
+    assert ROW_SWEEP in open(os.path.join(ROOT, CSRC, "Makefile")).read()
+    # structure_passes.hpp does not take the body in: it is built on coo.hpp and held to its own function list
+    assert "lane_group_rows" not in open(os.path.join(ROOT, CSRC, "structure_passes.hpp")).read()
+
+
 KERNELS = ("gs_census_kernel", "gs_round_kernel", "gs_keys_kernel", "gs_color_ptr_kernel", "gs_color_kernel")
 # as recorded in k_gs.hip's header comment
-RECORDED_VGPRS = dict(gs_census_kernel=26, gs_round_kernel=20, gs_keys_kernel=8, gs_color_ptr_kernel=9, gs_color_kernel=48)
+RECORDED_VGPRS = dict(gs_census_kernel=26, gs_round_kernel=20, gs_keys_kernel=8, gs_color_ptr_kernel=9, gs_color_kernel=47)
 
 
 def test_gs_kernels_fit_their_register_budget(tmp_path):

@@ -22,7 +22,7 @@ import spmv_acc_amd
 from test_amg_host import IRREGULAR_TAGS, problem, scaling
 from test_amg_host import TAGS as GRID_TAGS
 from test_coo_host import SHARED, _FakeTensor, _f, _i
-from test_gs_host import CHUNK_ROWS, HELPERS, TAGS, cases, lane_group, row_sum
+from test_gs_host import CHUNK_ROWS, HELPERS, ROW_SWEEP, TAGS, cases, lane_group, row_sum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -42,13 +42,13 @@ JACOBI_SIZE_RULES = [
      [CONTRACT], "more rows than 32-bit gather offsets reach: SPMV_ACC_ERR_TOO_LARGE on the host"),
     ("the row limit's refusal", CSRC + "jacobi.cpp", r"if \(m > kJacobiMaxRows\)",
      [CONTRACT], "the sweep refuses 2^29 + 1 rows before any launch"),
-    ("the lane group's rule", CSRC + "k_jacobi.hip", r"while \(g < kWave && static_cast<u64>\(g\) \* kGsTermsPerLane \* rows_here < terms\) \{",
+    ("the lane group's rule", CSRC + ROW_SWEEP, r"while \(g < kWave && static_cast<u64>\(g\) \* kGsTermsPerLane \* rows_here < terms\) \{",
      [DIAGONAL, SWEEP], "the smallest G with G * 4 * rows of the chunk >= the chunk's terms: G = 1 (path, lonely), 2 (grid7), 4 (fem), 8 (grid27), 16, "
                         "32 (the bands), 64 (k130); test_the_lane_groups_of_the_cases holds the cases to that"),
-    ("the passes of a chunk", CSRC + "k_jacobi.hip", r"for \(int done = wave \* per_pass; done < rows_here; done \+= \(kThreads / kWave\) \* per_pass\) \{",
+    ("the passes of a chunk", CSRC + ROW_SWEEP, r"for \(int done = wave \* per_pass; done < rows_here; done \+= \(kThreads / kWave\) \* per_pass\) \{",
      [DIAGONAL, SWEEP], "a chunk of fewer rows than passes x rows per pass leaves wavefronts without a pass (one: one row; k130's last chunk: 2 rows at G = 64)"),
-    ("tile loop", CSRC + "k_jacobi.hip",
-     r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\) \{ // \(block-uniform\)\n    const long long base = tile \* kJacobiTile",
+    ("tile loop", CSRC + ROW_SWEEP,
+     r"for \(long long tile = blockIdx\.x; tile < ntiles; tile \+= gridDim\.x\) \{ // \(block-uniform\)\n    const long long base = first \+ tile \* kGsTile",
      [STRIDE], "blocks stride over the chunks beyond the grid (the stride test: 1 331 chunks over 64 workgroups)"),
     ("row loops of the inverse diagonal and the zero start", CSRC + "k_jacobi.hip", r"r < m; r \+= stride\) \{",
      [STRIDE], "one row per lane, striding (the stride test: 85 184 rows over 64 workgroups)"),
@@ -58,7 +58,7 @@ JACOBI_SIZE_RULES = [
      [STRIDE], "the launchers take the shared grid"),
     ("a row without a diagonal", CSRC + "k_jacobi.hip", r"dinv\[i\] = has_diag \? 1\.0 / s : 0\.0;",
      [DIAGONAL], "+0.0 (fem_holes, grid7_holes, empties, one_empty); kind 0: the binary search misses"),
-    ("a column outside [0, m)", CSRC + "k_jacobi.hip", r"return static_cast<unsigned>\(t\.c\) >= static_cast<unsigned>\(m\) \? 0\.0 : w;",
+    ("a column outside [0, m)", CSRC + ROW_SWEEP, r"return static_cast<unsigned>\(t\.c\) >= static_cast<unsigned>\(m\) \? 0\.0 : w;",
      [CONTRACT], "the term +0.0, and no address is formed from the column"),
     ("the zero start", CSRC + "jacobi.cpp", r"if \(d_x_in\) launch_jacobi_sweep\(",
      [SWEEP, "test_captured_and_replayed"], "x_in == NULL: the one-row-per-lane kernel that does not read the matrix"),
@@ -86,9 +86,12 @@ def test_jacobi_size_rules_name_their_tests():
             found += 1
             assert k in registered, f"{f}: constant {k} is not in JACOBI_SIZE_RULES"
     assert found == 2
-    kernels = open(os.path.join(ROOT, CSRC, "k_jacobi.hip")).read()
-    assert kernels.count("tile += gridDim.x") == 1 and kernels.count("+= stride)") == 2  # every loop over work is one of the registered forms
-    assert kernels.count("jacobi_rows(m, nnz, rowptr, colindex, value, rows);") == 2  # the l1 diagonal and the sweep share one body
+    # every loop over work is one of the registered forms: the one tile loop stands in the shared body (kJacobiTile is kGsTile)
+    kernels, body = open(os.path.join(ROOT, CSRC, "k_jacobi.hip")).read(), open(os.path.join(ROOT, CSRC, ROW_SWEEP)).read()
+    assert body.count("tile += gridDim.x") == 1 and kernels.count("tile += gridDim.x") == 0 and kernels.count("+= stride)") == 2
+    assert "constexpr int kGsTile = kGsChunkRows;" in open(os.path.join(ROOT, CSRC, "gs.hpp")).read()
+    # the l1 diagonal and the sweep share that body with the Gauss-Seidel sweep: all rows are the one colour
+    assert kernels.count("lane_group_rows(m, nnz, rowptr, colindex, value, 0, m, rows);") == 2 and kernels.count("lane_group_rows(") == 2
 
 
 PROTOTYPES = (
@@ -277,7 +280,7 @@ def test_jacobi_entries_keep_no_state():
 
 KERNELS = ("jacobi_inverse_kernel", "jacobi_start_kernel", "jacobi_sweep_kernel", "jacobi_l1_kernel")
 # as recorded in k_jacobi.hip's header comment
-RECORDED_VGPRS = dict(jacobi_inverse_kernel=12, jacobi_start_kernel=10, jacobi_sweep_kernel=38, jacobi_l1_kernel=50)
+RECORDED_VGPRS = dict(jacobi_inverse_kernel=12, jacobi_start_kernel=10, jacobi_sweep_kernel=39, jacobi_l1_kernel=52)
 
 
 def test_jacobi_kernels_fit_their_register_budget(tmp_path):
