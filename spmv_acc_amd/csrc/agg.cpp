@@ -90,8 +90,7 @@ int run_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_colindex
   if (!launch_coo_scan(st, flag, m, id, ws + off_tmp, &scan_bytes)) return leave(entry_error(kEntry, kErrHip, "scan failed"));
   launch_agg_assign_roots(st, m, nnz, d_rowptr, d_colindex, flag, id, first);
   launch_agg_assign_rest(st, m, nnz, d_rowptr, d_colindex, first, d_agg, d_slots);
-  hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   int naggs = -1;
   if (!hip_ok(hipMemcpyAsync(&naggs, id + rows, sizeof(int), hipMemcpyDeviceToHost, st), "read the number of aggregates") ||
       !hip_ok(hipMemcpyAsync(slots.data(), d_slots, sizeof(unsigned) * kCooCheckSlots, hipMemcpyDeviceToHost, st), "read the unassigned count") ||
@@ -107,8 +106,7 @@ int run_csr_aggregate(int m, int nnz, const int *d_rowptr, const int *d_colindex
   launch_gs_keys(st, m, d_agg, keys);
   if (!launch_coo_sort(st, keys, m, key_bits, sorted, d_agg_rows, ws + off_tmp, &sort_bytes)) return leave(entry_error(kEntry, kErrHip, "radix sort failed"));
   launch_gs_color_ptr(st, m, sorted, m + 1, d_agg_ptr);
-  launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   if (!hip_ok(hipStreamSynchronize(st), "aggregation")) return leave(last_error_code_only());
   *h_naggs = naggs;
   return leave(kOk);
@@ -133,9 +131,7 @@ int run_csr_tentative_values(int m, int naggs, const int *d_agg, const int *d_ag
   note_stream_use();
   launch_agg_norms(st, m, naggs, d_agg_ptr, d_agg_rows, d_b, d_bc);
   launch_agg_values(st, m, naggs, d_agg, d_agg_rows, d_b, d_bc, d_p_value, d_r_value);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

@@ -46,12 +46,6 @@ int common_refusals(const char *entry, int n, const double *d_partials, const un
   return kOk;
 }
 
-int launched(const char *entry) {
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(entry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
-}
-
 } // namespace
 
 int run_cg_partials(int n, size_t *h_count) {
@@ -83,7 +77,7 @@ int run_cg_start(int n, double rtol, const double *d_b, const double *d_r, const
   note_stream_use();
   launch_cg_start_pass(st, n, d_b, d_r, d_z, d_p, d_partials);
   launch_cg_start_finish(st, n, rtol, d_partials, d_state, d_hist, hist_cap);
-  return launched(kEntry);
+  return launch_error(kEntry);
 }
 
 int run_cg_update(int n, const double *d_p, const double *d_q, double *d_x, double *d_r, double *d_partials, unsigned long long *d_state,
@@ -106,7 +100,7 @@ int run_cg_update(int n, const double *d_p, const double *d_q, double *d_x, doub
   launch_cg_pq_finish(st, n, d_partials, d_state);
   launch_cg_update_pass(st, n, d_p, d_q, d_x, d_r, d_state, d_partials);
   launch_cg_rr_finish(st, n, d_partials, d_state, d_hist, hist_cap);
-  return launched(kEntry);
+  return launch_error(kEntry);
 }
 
 int run_cg_direction(int n, const double *d_r, double *d_z, const double *d_dinv, double *d_p, double *d_partials, unsigned long long *d_state) {
@@ -132,7 +126,7 @@ int run_cg_direction(int n, const double *d_r, double *d_z, const double *d_dinv
   launch_cg_rz_pass(st, n, d_r, d_z, d_dinv, d_state, d_partials);
   launch_cg_rz_finish(st, n, d_partials, d_state);
   launch_cg_direction_pass(st, n, d_z, d_p, d_state);
-  return launched(kEntry);
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

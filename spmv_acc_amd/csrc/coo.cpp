@@ -6,41 +6,27 @@
 // of the same values repeats the first assembly's bits.
 #include "coo.hpp"
 #include "engine_internal.hpp"
+#include "entry_helpers.hpp"
 
 namespace spmv_acc {
 
 using namespace detail;
-
-namespace {
-
-int coo_error(const char *entry, int code, const std::string &what) {
-  set_error(code, std::string(entry) + ": " + what);
-  return code;
-}
-
-constexpr size_t kCooAlign = 256; // workspace parts start on 256-B boundaries
-size_t coo_aligned_up(size_t b) { return (b + kCooAlign - 1) / kCooAlign * kCooAlign; }
-
-// the m / n / nnz every entry of the library accepts (plan.cpp: room for block arithmetic in int32)
-bool coo_too_large(int v) { return v > INT_MAX - (1 << 16); }
-
-} // namespace
 
 int run_coo_to_csr(int m, int n, int nnz_coo, const int *d_row, const int *d_col, const double *d_val, int *d_rowptr, int *d_colindex,
                    double *d_value, int *d_order, int *d_start, int *h_nnz) {
   static const char *const kEntry = "spmv_acc_coo_to_csr";
   clear_error();
   apply_env_tunables();
-  if (m < 0 || n < 0 || nnz_coo < 0) return coo_error(kEntry, kErrBadArgument, "negative m, n or nnz_coo");
-  if (!d_rowptr || !h_nnz) return coo_error(kEntry, kErrBadArgument, "null rowptr / h_nnz");
+  if (m < 0 || n < 0 || nnz_coo < 0) return entry_error(kEntry, kErrBadArgument, "negative m, n or nnz_coo");
+  if (!d_rowptr || !h_nnz) return entry_error(kEntry, kErrBadArgument, "null rowptr / h_nnz");
   if ((d_val == nullptr) != (d_value == nullptr))
-    return coo_error(kEntry, kErrBadArgument, "val and value must both be given or both be NULL (structure only)");
+    return entry_error(kEntry, kErrBadArgument, "val and value must both be given or both be NULL (structure only)");
   if ((d_order == nullptr) != (d_start == nullptr))
-    return coo_error(kEntry, kErrBadArgument, "order and start must both be given or both be NULL (no map)");
-  if (coo_too_large(m) || coo_too_large(n) || coo_too_large(nnz_coo))
-    return coo_error(kEntry, kErrTooLarge, "m, n or nnz_coo does not leave room for block arithmetic in int32; assemble row ranges");
-  if (nnz_coo > 0 && (!d_row || !d_col || !d_colindex)) return coo_error(kEntry, kErrBadArgument, "null row / col / colindex with nnz_coo != 0");
-  if (nnz_coo > 0 && (m == 0 || n == 0)) return coo_error(kEntry, kErrBadArgument, "triples in a matrix without rows or columns");
+    return entry_error(kEntry, kErrBadArgument, "order and start must both be given or both be NULL (no map)");
+  if (too_large(m) || too_large(n) || too_large(nnz_coo))
+    return entry_error(kEntry, kErrTooLarge, "m, n or nnz_coo does not leave room for block arithmetic in int32; assemble row ranges");
+  if (nnz_coo > 0 && (!d_row || !d_col || !d_colindex)) return entry_error(kEntry, kErrBadArgument, "null row / col / colindex with nnz_coo != 0");
+  if (nnz_coo > 0 && (m == 0 || n == 0)) return entry_error(kEntry, kErrBadArgument, "triples in a matrix without rows or columns");
   hipStream_t st = t_stream;
   note_stream_use();
   const ScopedSet<bool> capture_flag(t_capturing, stream_capturing(st));
@@ -61,14 +47,14 @@ int run_coo_to_csr(int m, int n, int nnz_coo, const int *d_row, const int *d_col
   if (!launch_coo_sort(st, nullptr, nnz_coo, key_bits, nullptr, nullptr, nullptr, &sort_bytes) ||
       !launch_coo_scan(st, nullptr, nnz_coo, nullptr, nullptr, &scan_bytes)) {
     (void)hipGetLastError();
-    return coo_error(kEntry, kErrHip, "radix sort / scan workspace query failed");
+    return entry_error(kEntry, kErrHip, "radix sort / scan workspace query failed");
   }
-  const size_t keys_bytes = coo_aligned_up(sizeof(unsigned long long) * (count + 1)); // (+ 1: room for the two int arrays of count + 1 that follow)
-  const size_t ints = coo_aligned_up(sizeof(int) * (count + 1));
+  const size_t keys_bytes = aligned_up(sizeof(unsigned long long) * (count + 1)); // (+ 1: room for the two int arrays of count + 1 that follow)
+  const size_t ints = aligned_up(sizeof(int) * (count + 1));
   const size_t off_sorted = keys_bytes, off_order = off_sorted + keys_bytes, off_start = off_order + (d_order ? 0 : ints);
-  const size_t off_slots = off_start + (d_start ? 0 : ints), off_tmp = off_slots + coo_aligned_up(sizeof(unsigned) * kCooCheckSlots);
+  const size_t off_slots = off_start + (d_start ? 0 : ints), off_tmp = off_slots + aligned_up(sizeof(unsigned) * kCooCheckSlots);
   char *ws = nullptr;
-  if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&ws), off_tmp + coo_aligned_up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes)),
+  if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&ws), off_tmp + aligned_up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes)),
               "hipMalloc assembly workspace"))
     return last_error_code_only();
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws);
@@ -93,25 +79,23 @@ int run_coo_to_csr(int m, int n, int nnz_coo, const int *d_row, const int *d_col
          hip_ok(hipStreamSynchronize(st), "range census");
   }
   if (!ok) return leave(last_error_code_only());
-  unsigned long long bad = 0;
-  for (unsigned c : slots) bad += c;
+  const unsigned long long bad = slot_sum(slots.data());
   if (bad != 0)
-    return leave(coo_error(kEntry, kErrBadArgument,
-                           std::to_string(bad) + " triples with a row outside [0, m) or a column outside [0, n): nothing was written"));
+    return leave(entry_error(kEntry, kErrBadArgument,
+                             std::to_string(bad) + " triples with a row outside [0, m) or a column outside [0, n): nothing was written"));
   launch_coo_keys(st, d_row, d_col, nnz_coo, col_bits, keys);
-  if (!launch_coo_sort(st, keys, nnz_coo, key_bits, sorted, order, ws + off_tmp, &sort_bytes)) return leave(coo_error(kEntry, kErrHip, "radix sort failed"));
+  if (!launch_coo_sort(st, keys, nnz_coo, key_bits, sorted, order, ws + off_tmp, &sort_bytes)) return leave(entry_error(kEntry, kErrHip, "radix sort failed"));
   launch_coo_heads(st, sorted, nnz_coo, head);
-  if (!launch_coo_scan(st, head, nnz_coo, index, ws + off_tmp, &scan_bytes)) return leave(coo_error(kEntry, kErrHip, "scan failed"));
+  if (!launch_coo_scan(st, head, nnz_coo, index, ws + off_tmp, &scan_bytes)) return leave(entry_error(kEntry, kErrHip, "scan failed"));
   int nnz = 0; // the number of runs: the values' launch is sized by it
   if (!hip_ok(hipMemcpyAsync(&nnz, index + count, sizeof(int), hipMemcpyDeviceToHost, st), "read the number of distinct positions") ||
       !hip_ok(hipStreamSynchronize(st), "sort and scan"))
     return leave(last_error_code_only());
-  if (nnz < 1 || nnz > nnz_coo) return leave(coo_error(kEntry, kErrHip, "the scan of the run heads returned " + std::to_string(nnz)));
+  if (nnz < 1 || nnz > nnz_coo) return leave(entry_error(kEntry, kErrHip, "the scan of the run heads returned " + std::to_string(nnz)));
   launch_coo_entries(st, sorted, head, index, nnz_coo, col_bits, start, d_colindex);
   launch_coo_rowptr(st, sorted, index, nnz_coo, m, col_bits, d_rowptr);
   if (d_value) launch_coo_values(st, nnz_coo, nnz, order, start, d_val, d_value);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(coo_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   if (!hip_ok(hipStreamSynchronize(st), "assembly")) return leave(last_error_code_only());
   *h_nnz = nnz;
   return leave(kOk);
@@ -121,17 +105,15 @@ int run_coo_to_csr_values(int nnz_coo, int nnz, const int *d_order, const int *d
   static const char *const kEntry = "spmv_acc_coo_to_csr_values";
   clear_error();
   apply_env_tunables();
-  if (nnz_coo < 0 || nnz < 0) return coo_error(kEntry, kErrBadArgument, "negative nnz_coo or nnz");
-  if (coo_too_large(nnz_coo) || coo_too_large(nnz)) return coo_error(kEntry, kErrTooLarge, "nnz_coo or nnz does not leave room for block arithmetic in int32");
-  if (nnz > nnz_coo) return coo_error(kEntry, kErrBadArgument, "nnz > nnz_coo: more distinct positions than triples");
+  if (nnz_coo < 0 || nnz < 0) return entry_error(kEntry, kErrBadArgument, "negative nnz_coo or nnz");
+  if (too_large(nnz_coo) || too_large(nnz)) return entry_error(kEntry, kErrTooLarge, "nnz_coo or nnz does not leave room for block arithmetic in int32");
+  if (nnz > nnz_coo) return entry_error(kEntry, kErrBadArgument, "nnz > nnz_coo: more distinct positions than triples");
   if (nnz == 0) return kOk;
-  if (!d_order || !d_start || !d_val || !d_value) return coo_error(kEntry, kErrBadArgument, "null order / start / val / value");
+  if (!d_order || !d_start || !d_val || !d_value) return entry_error(kEntry, kErrBadArgument, "null order / start / val / value");
   hipStream_t st = t_stream;
   note_stream_use();
   launch_coo_values(st, nnz_coo, nnz, d_order, d_start, d_val, d_value);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return coo_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

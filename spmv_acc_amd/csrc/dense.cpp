@@ -68,8 +68,7 @@ int run_csr_dense_inverse(int m, int nnz, const int *d_rowptr, const int *d_coli
     launch_dense_update(st, m, k, E, prow, f);
   }
   launch_dense_copy(st, m, E, d_inv);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   unsigned long long info = 0;
   if (!hip_ok(hipMemcpyAsync(&info, state + 2, sizeof(info), hipMemcpyDeviceToHost, st), "read info") || !hip_ok(hipStreamSynchronize(st), "dense inverse"))
     return leave(last_error_code_only());
@@ -93,9 +92,7 @@ int run_dense_apply(int m, const double *d_inv, const double *d_b, double *d_x) 
   hipStream_t st = t_stream;
   note_stream_use();
   launch_dense_apply(st, m, d_inv, d_b, d_x);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

@@ -1,12 +1,13 @@
-// entry_helpers.hpp -- the host building blocks that the four entry files of the AMG chain share (gs.cpp, agg.cpp, strength.cpp, dense.cpp): one
-// definition each of the entry's error, the workspace alignment and its round-up, the int32 size rule, the overlap of two double arrays, the sum
-// of one group of count slots, and the pattern census (k_gs.hip's) with its judgement and its refusal text -- the input contract that all four
-// entries, and amg_setup through them, refuse in the same words.  Plain inline helpers: no state and no device allocation (the census' host copy
-// of the slots is a local, as it was in every entry).
+// entry_helpers.hpp -- the host building blocks that the stateless entry files share: the structural entries (coo.cpp, transpose.cpp, spmm.cpp,
+// spgemm.cpp, csr_add.cpp, extract.cpp) and the AMG chain and its solvers (gs.cpp, agg.cpp, strength.cpp, dense.cpp, cg.cpp, jacobi.cpp).  One
+// definition each of the entry's error, the check after an entry's launches, the workspace alignment and its round-up, the int32 size rule, the
+// overlap of two double arrays, the sum of one group of count slots, and the pattern census (k_gs.hip's) with its judgement and its refusal
+// text -- the input contract that the four AMG entries (gs, agg, strength, dense), and amg_setup through them, refuse in the same words.  Plain
+// inline helpers: no state and no device allocation (the census' host copy of the slots is a local, as it was in every entry).
 //
 // Deliberately not here: the leave lambda, the one hipMalloc / hipFree and the workspace layout of an entry, its preamble (clear_error, the
 // tunables, the capture flag, plan_work_allowed) and its argument checks -- they are what differs between the entries, and they stay where
-// the entry can be read from top to bottom.  The older structural entries (coo, transpose, spmm, spgemm, csr_add, extract) keep their own helpers.
+// the entry can be read from top to bottom.  Nor spmm.cpp's and dispatch.cpp's launch checks, which keep an error that is already pending.
 //
 // No reference counterpart: hpcde/spmv-acc reads a finished matrix from a file on the host.
 #pragma once
@@ -21,6 +22,13 @@ namespace detail {
 inline int entry_error(const char *entry, int code, const std::string &what) {
   set_error(code, std::string(entry) + ": " + what);
   return code;
+}
+
+// after an entry's launches: kOk, or the launch's failure left as the entry's error (one hipGetLastError)
+inline int launch_error(const char *entry) {
+  const hipError_t err = hipGetLastError();
+  if (err == hipSuccess) return kOk;
+  return entry_error(entry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(err));
 }
 
 constexpr size_t kEntryAlign = 256; // workspace parts start on 256-B boundaries

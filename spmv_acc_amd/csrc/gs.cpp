@@ -96,8 +96,7 @@ int run_csr_color(int m, int nnz, const int *d_rowptr, const int *d_colindex, in
   if (!launch_coo_sort(st, keys, m, key_bits, sorted, d_color_rows, ws + off_tmp, &sort_bytes))
     return leave(entry_error(kEntry, kErrHip, "radix sort failed"));
   launch_gs_color_ptr(st, m, sorted, ptr_count, d_ptr);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   if (!hip_ok(hipMemcpyAsync(&last_key, sorted + (rows - 1), sizeof(last_key), hipMemcpyDeviceToHost, st), "read the largest colour") ||
       !hip_ok(hipMemcpyAsync(ptr.data(), d_ptr, sizeof(int) * static_cast<size_t>(ptr_count), hipMemcpyDeviceToHost, st), "read the colour pointer") ||
       !hip_ok(hipStreamSynchronize(st), "colouring"))
@@ -138,9 +137,7 @@ int run_csr_gs_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex,
     for (int c = 0; c < ncolors; ++c) colour(c);
   if (direction != 0)
     for (int c = ncolors - 1; c >= 0; --c) colour(c);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

@@ -39,9 +39,7 @@ int run_csr_jacobi_diagonal(int m, int nnz, const int *d_rowptr, const int *d_co
     launch_strength_sd(st, m, nnz, d_rowptr, d_colindex, d_value, d_work);
     launch_jacobi_l1(st, m, nnz, d_rowptr, d_colindex, d_value, d_work, d_dinv);
   }
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 int run_csr_jacobi_sweep(int m, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, const double *d_dinv, double omega,
@@ -70,9 +68,7 @@ int run_csr_jacobi_sweep(int m, int nnz, const int *d_rowptr, const int *d_colin
   note_stream_use();
   if (d_x_in) launch_jacobi_sweep(st, m, nnz, d_rowptr, d_colindex, d_value, d_dinv, omega, d_b, d_x_in, d_x_out, d_r_out);
   else launch_jacobi_start(st, m, d_dinv, omega, d_b, d_x_out, d_r_out); // the zero start: the matrix is not read
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

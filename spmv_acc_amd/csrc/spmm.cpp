@@ -6,6 +6,7 @@
 // and it reads the caller's colindex / values on every call (no plan-resident copy or encoding of caller data).  Its shape is a rule on (m, nnz,
 // k, layout), so an SpMM is bitwise reproducible from its first call.
 #include "engine_internal.hpp"
+#include "entry_helpers.hpp"
 #include "spmm.hpp"
 
 namespace spmv_acc {
@@ -16,11 +17,6 @@ namespace {
 
 constexpr int kSpmmRowMajor = 0; // SPMV_ACC_ROW_MAJOR (the engine does not include the C header)
 constexpr int kSpmmColMajor = 1; // SPMV_ACC_COL_MAJOR
-
-int spmm_error(int code, const char *what) {
-  set_error(code, std::string("spmv_acc_csr_spmm: ") + what);
-  return code;
-}
 
 // The plan's SpMM section: the rows longer than kSpmmLongRow, cut into pieces of kSpmmPiece non-zeros, and the pieces' partial-sum scratch.
 // Built once per plan from rowptr (the caller's host copy when it passes one, else one read of the device array); refused inside a capture.
@@ -77,17 +73,18 @@ bool ensure_spmm(Plan &p, const int *h_rowptr, hipStream_t st) {
 
 int run_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz, const int *h_rowptr, const int *d_rowptr, const int *d_colindex,
              const double *d_value, const double *dX, long long ldx, double *dY, long long ldy) {
+  static const char *const kEntry = "spmv_acc_csr_spmm";
   clear_error();
   apply_env_tunables();
-  if (layout != kSpmmRowMajor && layout != kSpmmColMajor) return spmm_error(kErrBadArgument, "layout must be SPMV_ACC_ROW_MAJOR or SPMV_ACC_COL_MAJOR");
-  if (k < 0 || m < 0 || n < 0) return spmm_error(kErrBadArgument, "negative k, m or n");
+  if (layout != kSpmmRowMajor && layout != kSpmmColMajor) return entry_error(kEntry, kErrBadArgument, "layout must be SPMV_ACC_ROW_MAJOR or SPMV_ACC_COL_MAJOR");
+  if (k < 0 || m < 0 || n < 0) return entry_error(kEntry, kErrBadArgument, "negative k, m or n");
   const bool row_major = layout == kSpmmRowMajor;
   if (row_major ? (ldx < k || ldy < k) : (ldx < n || ldy < m))
-    return spmm_error(kErrBadArgument, row_major ? "row-major needs ldx >= k and ldy >= k" : "column-major needs ldx >= n and ldy >= m");
+    return entry_error(kEntry, kErrBadArgument, row_major ? "row-major needs ldx >= k and ldy >= k" : "column-major needs ldx >= n and ldy >= m");
   if (k == 0 || m == 0) return kOk;
-  if (!d_rowptr || !dY || (n > 0 && !dX)) return spmm_error(kErrBadArgument, "null rowptr / X / Y");
-  if (nnz != 0 && n > 0 && (!d_colindex || !d_value)) return spmm_error(kErrBadArgument, "null colindex / value with nnz != 0");
-  if (m > INT_MAX - (1 << 16)) return spmm_error(kErrTooLarge, "row count does not leave room for block arithmetic in int32; shard the matrix");
+  if (!d_rowptr || !dY || (n > 0 && !dX)) return entry_error(kEntry, kErrBadArgument, "null rowptr / X / Y");
+  if (nnz != 0 && n > 0 && (!d_colindex || !d_value)) return entry_error(kEntry, kErrBadArgument, "null colindex / value with nnz != 0");
+  if (too_large(m)) return entry_error(kEntry, kErrTooLarge, "row count does not leave room for block arithmetic in int32; shard the matrix");
 
   // k == 1 with contiguous vectors (the two layouts coincide): the SpMV path under the active strategy, bitwise what spmv_acc_csr_spmv gives
   if (k == 1 && (!row_major || (ldx == 1 && ldy == 1))) {
@@ -101,7 +98,7 @@ int run_spmm(int layout, int k, double alpha, double beta, int m, int n, int nnz
     launch_spmm_scale(st, m, k, row_major, ldy, beta, dY);
   } else {
     const std::shared_ptr<Plan> p = get_plan(m, n, nnz, h_rowptr, d_rowptr, d_colindex, d_value);
-    if (!p) return last_error_code_only() != kOk ? last_error_code_only() : spmm_error(kErrHip, "no plan");
+    if (!p) return last_error_code_only() != kOk ? last_error_code_only() : entry_error(kEntry, kErrHip, "no plan");
     t_last_plan = p; // (spmv_acc_last_error reports a stale plan found by this call's kernels, as after an SpMV)
     std::lock_guard<std::mutex> plan_lock(p->mu);
     if (p->A.count() == 0) {

@@ -73,8 +73,7 @@ int run_csr_strength(int m, int nnz, const int *d_rowptr, const int *d_colindex,
   if (!launch_coo_scan(st, flag, nnz, pos, ws + off_tmp, &scan_bytes)) return leave(entry_error(kEntry, kErrHip, "scan failed"));
   launch_strength_ptrs(st, m, nnz, d_rowptr, pos, d_s_rowptr, d_drop_ptr);
   launch_strength_scatter(st, nnz, d_colindex, flag, pos, d_s_colindex, d_map);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   int nnz_s = -1;
   if (!hip_ok(hipMemcpyAsync(&nnz_s, pos + entries, sizeof(int), hipMemcpyDeviceToHost, st), "read the number of kept entries") ||
       !hip_ok(hipStreamSynchronize(st), "strength filter"))
@@ -107,9 +106,7 @@ int run_csr_strength_values(int m, int nnz, int nnz_s, const int *d_s_rowptr, co
   note_stream_use();
   launch_strength_diag(st, m, nnz, nnz_s, d_s_rowptr, d_s_colindex, d_map, d_drop_ptr, d_value, d_diag);
   launch_strength_values(st, m, nnz, nnz_s, d_s_rowptr, d_s_colindex, d_map, d_value, d_diag, omega, d_s_value);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return entry_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

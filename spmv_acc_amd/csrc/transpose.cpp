@@ -5,39 +5,25 @@
 // the caller (who then runs any entry of the library on them: the whole tuned engine serves A^T), and the stateless product reads the caller's
 // CSR on every call.  The `trans` argument of the other entries keeps its reported-not-applied behaviour.
 #include "engine_internal.hpp"
+#include "entry_helpers.hpp"
 #include "transpose.hpp"
 
 namespace spmv_acc {
 
 using namespace detail;
 
-namespace {
-
-int trans_error(const char *entry, int code, const std::string &what) {
-  set_error(code, std::string(entry) + ": " + what);
-  return code;
-}
-
-constexpr size_t kTransAlign = 256; // workspace parts start on 256-B boundaries
-size_t aligned_up(size_t b) { return (b + kTransAlign - 1) / kTransAlign * kTransAlign; }
-
-// the m / n / nnz every entry of the library accepts (plan.cpp: room for block arithmetic in int32)
-bool too_large(int v) { return v > INT_MAX - (1 << 16); }
-
-} // namespace
-
 int run_csr_transpose(int m, int n, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value, int *d_t_rowptr,
                       int *d_t_colindex, double *d_t_value, int *d_perm) {
   static const char *const kEntry = "spmv_acc_csr_transpose";
   clear_error();
   apply_env_tunables();
-  if (m < 0 || n < 0) return trans_error(kEntry, kErrBadArgument, "negative m or n");
-  if (!d_t_rowptr) return trans_error(kEntry, kErrBadArgument, "null t_rowptr");
+  if (m < 0 || n < 0) return entry_error(kEntry, kErrBadArgument, "negative m or n");
+  if (!d_t_rowptr) return entry_error(kEntry, kErrBadArgument, "null t_rowptr");
   if ((d_value == nullptr) != (d_t_value == nullptr))
-    return trans_error(kEntry, kErrBadArgument, "value and t_value must both be given or both be NULL (structure only)");
+    return entry_error(kEntry, kErrBadArgument, "value and t_value must both be given or both be NULL (structure only)");
   if (too_large(m) || too_large(n) || too_large(nnz))
-    return trans_error(kEntry, kErrTooLarge, "m, n or nnz does not leave room for block arithmetic in int32; shard the matrix");
-  if (m > 0 && nnz != 0 && !d_rowptr) return trans_error(kEntry, kErrBadArgument, "null rowptr");
+    return entry_error(kEntry, kErrTooLarge, "m, n or nnz does not leave room for block arithmetic in int32; shard the matrix");
+  if (m > 0 && nnz != 0 && !d_rowptr) return entry_error(kEntry, kErrBadArgument, "null rowptr");
   hipStream_t st = t_stream;
   note_stream_use();
   const ScopedSet<bool> capture_flag(t_capturing, stream_capturing(st));
@@ -49,26 +35,26 @@ int run_csr_transpose(int m, int n, int nnz, const int *d_rowptr, const int *d_c
         !hip_ok(hipStreamSynchronize(st), "read rowptr[0], rowptr[m]"))
       return last_error_code_only();
     if (ends[0] != 0)
-      return trans_error(kEntry, kErrBadArgument, "rowptr[0] != 0: an un-rebased row sub-range cannot be transposed in place; rebase it first");
-    if (ends[1] < 0 || (nnz >= 0 && ends[1] != nnz)) return trans_error(kEntry, kErrBadArgument, "nnz is not rowptr[m]");
+      return entry_error(kEntry, kErrBadArgument, "rowptr[0] != 0: an un-rebased row sub-range cannot be transposed in place; rebase it first");
+    if (ends[1] < 0 || (nnz >= 0 && ends[1] != nnz)) return entry_error(kEntry, kErrBadArgument, "nnz is not rowptr[m]");
     nnz = ends[1];
-    if (too_large(nnz)) return trans_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32; shard the matrix");
+    if (too_large(nnz)) return entry_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32; shard the matrix");
   }
   if (m == 0 || n == 0 || nnz <= 0) { // an empty matrix: t_rowptr is all zeros, nothing else is written
-    if (nnz > 0 && n == 0) return trans_error(kEntry, kErrBadArgument, "non-zeros in a matrix without columns");
+    if (nnz > 0 && n == 0) return entry_error(kEntry, kErrBadArgument, "non-zeros in a matrix without columns");
     if (!hip_ok(hipMemsetAsync(d_t_rowptr, 0, sizeof(int) * (static_cast<size_t>(n) + 1), st), "zero t_rowptr")) return last_error_code_only();
     return kOk;
   }
-  if (!d_colindex || !d_t_colindex) return trans_error(kEntry, kErrBadArgument, "null colindex / t_colindex with nnz != 0");
+  if (!d_colindex || !d_t_colindex) return entry_error(kEntry, kErrBadArgument, "null colindex / t_colindex with nnz != 0");
 
   // one allocation: the sorted keys (then each non-zero's row), perm when the caller wants none, the census counter, the sort's scratch
   size_t sort_bytes = 0;
   if (!launch_transpose_sort(st, d_colindex, nnz, n, nullptr, nullptr, nullptr, &sort_bytes)) {
     (void)hipGetLastError();
-    return trans_error(kEntry, kErrHip, "radix sort workspace query failed");
+    return entry_error(kEntry, kErrHip, "radix sort workspace query failed");
   }
   const size_t ints = aligned_up(sizeof(int) * static_cast<size_t>(nnz));
-  const size_t off_perm = ints, off_bad = off_perm + (d_perm ? 0 : ints), off_sort = off_bad + kTransAlign;
+  const size_t off_perm = ints, off_bad = off_perm + (d_perm ? 0 : ints), off_sort = off_bad + kEntryAlign;
   char *ws = nullptr;
   if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&ws), off_sort + aligned_up(sort_bytes)), "hipMalloc transpose workspace")) return last_error_code_only();
   int *keys = reinterpret_cast<int *>(ws);
@@ -90,13 +76,12 @@ int run_csr_transpose(int m, int n, int nnz, const int *d_rowptr, const int *d_c
   }
   if (!ok) return leave(last_error_code_only());
   if (bad != 0)
-    return leave(trans_error(kEntry, kErrBadArgument, std::to_string(bad) + " column indices outside [0, n): nothing was written"));
-  if (!launch_transpose_sort(st, d_colindex, nnz, n, keys, perm, ws + off_sort, &sort_bytes)) return leave(trans_error(kEntry, kErrHip, "radix sort failed"));
+    return leave(entry_error(kEntry, kErrBadArgument, std::to_string(bad) + " column indices outside [0, n): nothing was written"));
+  if (!launch_transpose_sort(st, d_colindex, nnz, n, keys, perm, ws + off_sort, &sort_bytes)) return leave(entry_error(kEntry, kErrHip, "radix sort failed"));
   launch_transpose_rowptr(st, keys, nnz, n, d_t_rowptr);
   launch_transpose_rows(st, d_rowptr, m, nnz, keys); // (the sorted keys have served: their array now holds each non-zero's row)
   launch_transpose_gather(st, nnz, perm, keys, d_value, d_t_colindex, d_t_value);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return leave(trans_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err)));
+  if (const int rc = launch_error(kEntry)) return leave(rc);
   if (!hip_ok(hipStreamSynchronize(st), "transpose")) return leave(last_error_code_only());
   return leave(kOk);
 }
@@ -105,16 +90,14 @@ int run_csr_transpose_values(int nnz, const int *d_perm, const double *d_value, 
   static const char *const kEntry = "spmv_acc_csr_transpose_values";
   clear_error();
   apply_env_tunables();
-  if (nnz < 0) return trans_error(kEntry, kErrBadArgument, "negative nnz");
-  if (too_large(nnz)) return trans_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32");
+  if (nnz < 0) return entry_error(kEntry, kErrBadArgument, "negative nnz");
+  if (too_large(nnz)) return entry_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32");
   if (nnz == 0) return kOk;
-  if (!d_perm || !d_value || !d_t_value) return trans_error(kEntry, kErrBadArgument, "null perm / value / t_value");
+  if (!d_perm || !d_value || !d_t_value) return entry_error(kEntry, kErrBadArgument, "null perm / value / t_value");
   hipStream_t st = t_stream;
   note_stream_use();
   launch_transpose_values(st, nnz, d_perm, d_value, d_t_value);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return trans_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 int run_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *d_rowptr, const int *d_colindex, const double *d_value,
@@ -122,17 +105,17 @@ int run_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *
   static const char *const kEntry = "spmv_acc_csr_spmv_t";
   clear_error();
   apply_env_tunables();
-  if (m < 0 || n < 0) return trans_error(kEntry, kErrBadArgument, "negative m or n");
+  if (m < 0 || n < 0) return entry_error(kEntry, kErrBadArgument, "negative m or n");
   if (too_large(m) || too_large(n) || too_large(nnz))
-    return trans_error(kEntry, kErrTooLarge, "m, n or nnz does not leave room for block arithmetic in int32; shard the matrix");
+    return entry_error(kEntry, kErrTooLarge, "m, n or nnz does not leave room for block arithmetic in int32; shard the matrix");
   if (g_tunables[kT_deterministic].val > 0)
-    return trans_error(kEntry, kErrBadArgument,
+    return entry_error(kEntry, kErrBadArgument,
                        "tunable deterministic = 1: this entry adds with fp64 atomics, its sums depend on arrival order; transpose once with "
                        "spmv_acc_csr_transpose and run spmv_acc_csr_spmv on the result (bitwise reproducible); nothing was enqueued");
   if (n == 0) return kOk; // (y is empty)
-  if (!dy) return trans_error(kEntry, kErrBadArgument, "null y");
+  if (!dy) return entry_error(kEntry, kErrBadArgument, "null y");
   const bool product = m > 0 && nnz != 0 && alpha != 0.0;
-  if (product && (!d_rowptr || !d_colindex || !d_value || !dx)) return trans_error(kEntry, kErrBadArgument, "null rowptr / colindex / value / x");
+  if (product && (!d_rowptr || !d_colindex || !d_value || !dx)) return entry_error(kEntry, kErrBadArgument, "null rowptr / colindex / value / x");
   hipStream_t st = t_stream;
   note_stream_use();
   if (product && nnz < 0) { // the view's end offset from the device: the one case that synchronises
@@ -141,14 +124,12 @@ int run_csr_spmv_t(double alpha, double beta, int m, int n, int nnz, const int *
     if (!hip_ok(hipMemcpyAsync(&nnz, d_rowptr + m, sizeof(int), hipMemcpyDeviceToHost, st), "read rowptr[m]") ||
         !hip_ok(hipStreamSynchronize(st), "read rowptr[m]"))
       return last_error_code_only();
-    if (nnz < 0) return trans_error(kEntry, kErrBadArgument, "rowptr[m] is negative");
-    if (too_large(nnz)) return trans_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32; shard the matrix");
+    if (nnz < 0) return entry_error(kEntry, kErrBadArgument, "rowptr[m] is negative");
+    if (too_large(nnz)) return entry_error(kEntry, kErrTooLarge, "nnz does not leave room for block arithmetic in int32; shard the matrix");
   }
   if (beta != 1.0) launch_spmv_t_scale(st, n, beta, dy);
   if (product && nnz > 0) launch_spmv_t_scatter(st, m, n, nnz, alpha, d_rowptr, d_colindex, d_value, dx, dy);
-  const hipError_t launch_err = hipGetLastError();
-  if (launch_err != hipSuccess) return trans_error(kEntry, kErrHip, std::string("kernel launch failed: ") + hipGetErrorString(launch_err));
-  return kOk;
+  return launch_error(kEntry);
 }
 
 } // namespace spmv_acc

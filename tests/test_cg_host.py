@@ -360,7 +360,7 @@ def test_cg_entries_keep_no_state():
         assert re.findall(r"\blaunch_\w+(?=\(st, )", body) == list(launches), entry  # two, four and three launches, in the documented order
         before = body.split(launches[0] + "(")[0]
         assert before.count("first_overlap(") >= 1 and "common_refusals(kEntry, n, d_partials, d_state)" in before  # refused before any launch
-        assert body.index("note_stream_use();") < body.index(launches[0] + "(") and body.rstrip().endswith("return launched(kEntry);")
+        assert body.index("note_stream_use();") < body.index(launches[0] + "(") and body.rstrip().endswith("return launch_error(kEntry);")
     partials = code.split("int run_cg_partials(")[1].split("\n}\n")[0]
     assert "launch_" not in partials and "t_stream" not in partials  # host arithmetic only
     kernels = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, CSRC, "k_cg.hip")).read())

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
 NEW_SOURCES = ("coo.hpp", "k_coo.hip", "coo.cpp")
 SHARED = "structure_passes.hpp"  # what the structure-pass kernel files share: the other features' tables name it too
+HELPERS = "entry_helpers.hpp"  # what the entry files share on the host: the other features' tables name it too (test_gs_host.py holds it to its list)
 LONG_RUN = 64  # kCooLongRun (test_coo_size_rules_name_their_tests holds the two together)
 
 # (rule, file, regex that must match the source, GPU tests of tests/test_gpu_coo.py that cross it at test size, what it selects)
@@ -59,11 +60,11 @@ COO_SIZE_RULES = [
      ["test_assembly_is_the_host_stable_sort"], "the library sort picks its algorithm by size: lists of 1 ... 3.2 M triples cross its single-block, merge and multi-pass forms"),
     ("scan size paths", CSRC + "k_coo.hip", r"rocprim::exclusive_scan\(tmp, \*tmp_bytes, head, index, 0, static_cast<size_t>\(nnz_coo\) \+ 1,",
      ["test_assembly_is_the_host_stable_sort"], "the library scan: 2 ... 3.2 M + 1 flags"),
-    ("int32 block arithmetic", CSRC + "coo.cpp", r"bool coo_too_large\(int v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      ["test_coo_contract"], "m, n, nnz_coo or nnz beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
     ("workspace with / without the map", CSRC + "coo.cpp", r"off_start = off_order \+ \(d_order \? 0 : ints\)",
      ["test_assembly_is_the_host_stable_sort"], "order == start == NULL: the map lives in the workspace (24 B instead of 16 B per triple)"),
-    ("kCooAlign", CSRC + "coo.cpp", r"constexpr size_t kCooAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      ["test_assembly_is_the_host_stable_sort"], "workspace parts are padded to 256 B (nnz_coo not a multiple of 64: the 8 000-triple case)"),
     ("no triples", CSRC + "coo.cpp", r"if \(nnz_coo == 0\) \{",
      ["test_coo_contract"], "an empty list: rowptr zeroed, nothing allocated"),

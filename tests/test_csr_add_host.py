@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
-from test_coo_host import SHARED, _FakeTensor, _f, _i
+from test_coo_host import HELPERS, SHARED, _FakeTensor, _f, _i
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -68,9 +68,9 @@ CSR_ADD_SIZE_RULES = [
      [GPU], "an empty B (or A: if (nnz_a <= 0) return;) skips its place pass; the other matrix is copied, scaled"),
     ("workspace with / without the map", CSRC + "csr_add.cpp", r"const bool own_map = d_ia == nullptr && d_c_value != nullptr;",
      [GPU], "values without a caller's map: ia and ib live in the workspace (8 B per possible entry more); structure only without a map: none is written"),
-    ("kCsrAddAlign", CSRC + "csr_add.cpp", r"constexpr size_t kCsrAddAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [GPU], "workspace parts are padded to 256 B (counts that are no multiple of 64: most cases)"),
-    ("int32 block arithmetic", CSRC + "csr_add.cpp", r"bool csr_add_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      ["test_csr_add_contract"], "m, n, nnz_a, nnz_b or nnz_a + nnz_b beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
 ]
 
@@ -86,7 +86,7 @@ def test_csr_add_size_rules_name_their_tests():
     # every named constant of the new files is registered above (tests/size_thresholds.py does not scan them)
     registered = " ".join(r[0] + " " + r[2] for r in CSR_ADD_SIZE_RULES)
     found = 0
-    for f in NEW_SOURCES:
+    for f in NEW_SOURCES + (HELPERS,):  # (csr_add.cpp holds none since its alignment is the shared header's)
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             found += 1
             assert k in registered, f"{f}: constant {k} is not in CSR_ADD_SIZE_RULES"

@@ -287,7 +287,7 @@ def test_dense_entries_keep_no_state():
     assert body.count("hipMemcpyAsync(") == 1 and "while (" not in code  # info (the census' one copy is the helper's, pinned in test_gs_host): the host reads the elimination's state once
     apply = code.split("int run_dense_apply")[1]
     assert "hipMalloc" not in apply and "Synchronize" not in apply and "hipMemcpy" not in apply and "hipMemset" not in apply  # launch-only
-    assert "plan_work_allowed" not in apply and apply.count("launch_dense_apply(") == 1 and len(re.findall(r"\blaunch_\w+\(", apply)) == 1
+    assert "plan_work_allowed" not in apply and re.findall(r"\blaunch_\w+\(", apply) == ["launch_dense_apply(", "launch_error("]
     assert apply.index("b overlaps x") < apply.index("overlaps inv") < apply.index("launch_dense_apply(")  # refused before any launch
     kernels = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, CSRC, "k_dense.hip")).read())
     assert "atomic" not in kernels.lower() and "while (" not in kernels

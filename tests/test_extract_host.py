@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
-from test_coo_host import SHARED, _FakeTensor, _f, _i
+from test_coo_host import HELPERS, SHARED, _FakeTensor, _f, _i
 from test_csr_add_host import dense_of, random_sorted_csr, same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,7 +36,7 @@ EXTRACT_SIZE_RULES = [
     ("kExtractRankTile", CSRC + "extract.hpp", r"constexpr int kExtractRankTile = 256;",
      [GPU, STRIDE], "items per workgroup of the candidates, the scatter, the descents and the keys: 256, a wavefront 64 consecutive ones -- inside "
                     "one row (hub_row), across rows, across empty rows (empties)"),
-    ("kExtractAlign", CSRC + "extract.cpp", r"constexpr size_t kExtractAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [GPU], "workspace parts are padded to 256 B (counts that are no multiple of 64: most cases)"),
     ("kExtractCounts", CSRC + "extract.cpp", r"constexpr int kExtractCounts = 7;",
      [GPU, CONTRACT], "seven groups of per-wavefront counts: the census' five, the candidates' columns, the descents"),
@@ -82,7 +82,7 @@ EXTRACT_SIZE_RULES = [
      [GPU], "every candidate dropped (all_dropped, lo_above_hi): c_rowptr zeroed, nothing else written"),
     ("workspace with / without the map", CSRC + "extract.cpp", r"const bool own_map = d_map == nullptr && d_c_value != nullptr;",
      [GPU], "values without a caller's map (no_map): it lives in the workspace, 4 B per candidate more; structure only without a map: none is written"),
-    ("int32 block arithmetic", CSRC + "extract.cpp", r"bool extract_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      [CONTRACT], "m, n, mc, nc or nnz_a beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
 ]
 
@@ -98,7 +98,7 @@ def test_extract_size_rules_name_their_tests():
     # every named constant of the new files is registered above (tests/size_thresholds.py does not scan them)
     registered = " ".join(r[0] + " " + r[2] for r in EXTRACT_SIZE_RULES)
     found = 0
-    for f in NEW_SOURCES:
+    for f in NEW_SOURCES + (HELPERS,):  # (the alignment is the shared header's)
         for k in re.findall(r"constexpr\s+[\w:<> ]+?\s+(k[A-Z]\w*)\s*=", open(os.path.join(ROOT, CSRC, f)).read()):
             found += 1
             assert k in registered, f"{f}: constant {k} is not in EXTRACT_SIZE_RULES"
@@ -288,7 +288,7 @@ def test_extract_entries_keep_no_state():
     no_lambdas = re.sub(r"const auto nothing_kept = .*?\n  \};", "", after, flags=re.S)
     bare = [ln.strip() for ln in no_lambdas.splitlines() if re.search(r"\breturn\b(?! leave\()(?! nothing_kept\(\))", ln)]
     # (the one way out that may skip leave(): the scratch query before the first allocation)
-    assert bare == ['return extract_error(kEntry, kErrHip, "scan workspace query failed");'], bare
+    assert bare == ['return entry_error(kEntry, kErrHip, "scan workspace query failed");'], bare
     values = code.split("int run_csr_extract_values")[1]
     assert "hipMalloc" not in values and "Synchronize" not in values and "hipMemcpy" not in values and "hipMemset" not in values  # launch-only: capturable
     assert values.count("launch_extract_values(") == 1 and "launch_extract_" not in values.replace("launch_extract_values(", "")  # one kernel

@@ -16,15 +16,16 @@ import pytest
 
 import spmv_acc_amd
 from spmv_acc_amd import synth
-from test_coo_host import SHARED, _FakeTensor, _f, _i, host_assemble
+from test_coo_host import HELPERS, SHARED, _FakeTensor, _f, _i, host_assemble  # (HELPERS: defined below the files this one imports from)
 from test_extract_host import host_csr_permute
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
 NEW_SOURCES = ("gs.hpp", "k_gs.hip", "gs.cpp")
-HELPERS = "entry_helpers.hpp"  # what the four entry files of the AMG chain share: the other features' tables name it too
 ROW_SWEEP = "row_sweep.hpp"  # the one row-sum body of gs_color_kernel and the two Jacobi kernels: test_jacobi_host.py's table names it too
-ENTRY_FILES = ("gs.cpp", "agg.cpp", "strength.cpp", "dense.cpp")
+ENTRY_FILES = ("gs.cpp", "agg.cpp", "strength.cpp", "dense.cpp")  # the four that share the pattern census
+SOLVER_FILES = ("cg.cpp", "jacobi.cpp")
+STRUCTURAL_FILES = ("coo.cpp", "transpose.cpp", "spmm.cpp", "spgemm.cpp", "csr_add.cpp", "extract.cpp")
 COLOR = "test_color_is_the_host_model"
 SWEEP = "test_sweep_is_the_host_model"
 STRIDE = "test_gs_grid_stride_at_test_size"
@@ -300,14 +301,15 @@ def test_gs_entries_keep_no_state():
 
 
 def test_entry_helpers_keep_no_state():
-    """What gs.cpp, agg.cpp, strength.cpp and dense.cpp share on the host keeps nothing either: plain inline functions, no static, no device
-    allocation; the census is one memset, one launch, one copy and one synchronise, in that order, and its refusal text stands here alone."""
+    """What the entry files share on the host keeps nothing either: plain inline functions, no static, no device allocation; the census of
+    gs.cpp, agg.cpp, strength.cpp and dense.cpp is one memset, one launch, one copy and one synchronise, in that order, and its refusal text
+    stands here alone; and no entry file, structural, AMG or solver, keeps a copy of a helper or of the check after its launches."""
     code = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, CSRC, HELPERS)).read())
     for word in ("get_plan", "g_plans", "t_plan_work", "t_last_plan", "tune_", "TimingPhase", "TuneTimer", "static std::", "thread_local", "g_tunables"):
         assert word not in code, word
     assert not re.search(r"\bstatic\b", code) and "hipMalloc" not in code and "hipFree" not in code
     functions = re.findall(r"^(\w[\w ]*?)\b(\w+)\(", code, flags=re.M)
-    assert [name for _, name in functions] == ["entry_error", "aligned_up", "too_large", "overlap", "slot_sum", "pattern_census"], functions
+    assert [name for _, name in functions] == ["entry_error", "launch_error", "aligned_up", "too_large", "overlap", "slot_sum", "pattern_census"], functions
     assert all(kind.startswith("inline ") for kind, _ in functions), functions
     census = code.split("inline int pattern_census(hipStream_t st, const char *entry, ")[1].split("\n}\n")[0]
     calls = ("hipMemsetAsync(", "launch_gs_census(", "hipMemcpyAsync(", "hipStreamSynchronize(")
@@ -331,6 +333,24 @@ def test_entry_helpers_keep_no_state():
         assert not re.search(r"\b(gs|agg|strength|dense)_(error|too_large|aligned_up|overlap)\(", entry), f
         assert set(re.findall(r"\b(\w*(?:too_large|aligned_up|overlap))\(", entry)) <= {"too_large", "aligned_up", "overlap"}, f
         assert not re.search(r"constexpr size_t k\w*Align", entry), f
+    # nor does a structural entry file or a solver's keep a copy: the error, the round-up, the size rule, a written-out slot sum
+    for f in ENTRY_FILES + SOLVER_FILES + STRUCTURAL_FILES:
+        entry = open(os.path.join(ROOT, CSRC, f)).read()
+        assert '#include "' + HELPERS + '"' in entry, f
+        assert not re.search(r"\b(coo|trans|spgemm|csr_add|extract|spmm|cg|jacobi)_(error|too_large|aligned_up)\(", entry), f
+        assert not re.search(r"constexpr size_t k\w*Align", entry) and "INT_MAX - (1 << 16)" not in entry, f
+        for gone in ("kCooCheckSlots; ++s", "for (unsigned c : slots)", "set_error(code, std::string(entry)"):
+            assert gone not in entry, (f, gone)
+        if f not in SOLVER_FILES:  # (cg.cpp's first_overlap is a table walk on overlap())
+            assert set(re.findall(r"\b(\w*(?:too_large|aligned_up|overlap))\(", entry)) <= {"too_large", "aligned_up", "overlap"}, f
+        # the check after an entry's launches stands in the header alone; spmm.cpp's keeps a pending error and is its own
+        if f != "spmm.cpp":
+            assert "kernel launch failed" not in entry and not re.search(r"\blaunch_err\b", entry) and "hipGetErrorString" not in entry, f
+            assert "launch_error(kEntry)" in entry, f
+    assert code.count('"kernel launch failed: "') == 1 and code.count("hipGetErrorString(") == 1 and not re.search(r"\blaunch_err\b", code)
+    launch_check = code.split("inline int launch_error(const char *entry) {")[1].split("\n}\n")[0]
+    assert launch_check.count("hipGetLastError()") == 1 and code.count("hipGetLastError()") == 1
+    assert "return kOk;" in launch_check and "entry_error(entry, kErrHip, " in launch_check
     assert HELPERS in open(os.path.join(ROOT, CSRC, "Makefile")).read()
 
 

@@ -266,8 +266,8 @@ def test_jacobi_entries_keep_no_state():
         assert word not in code, word
     assert '#include "' + HELPERS + '"' in src and '#include "strength.hpp"' in src
     diagonal, sweep = code.split("int run_csr_jacobi_diagonal")[1].split("int run_csr_jacobi_sweep")
-    assert re.findall(r"\blaunch_\w+\(", diagonal) == ["launch_jacobi_inverse(", "launch_strength_sd(", "launch_jacobi_l1("]
-    assert re.findall(r"\blaunch_\w+\(", sweep) == ["launch_jacobi_sweep(", "launch_jacobi_start("]  # one launch, either form
+    assert re.findall(r"\blaunch_\w+\(", diagonal) == ["launch_jacobi_inverse(", "launch_strength_sd(", "launch_jacobi_l1(", "launch_error("]
+    assert re.findall(r"\blaunch_\w+\(", sweep) == ["launch_jacobi_sweep(", "launch_jacobi_start(", "launch_error("]  # one launch, either form
     for body in (diagonal, sweep):  # every refusal stands before the stream is taken
         assert body.index("hipStream_t st = t_stream;") > max(mt.start() for mt in re.finditer(r"return entry_error\(kEntry, kErr(BadArgument|TooLarge)", body))
         assert body.index("if (m == 0) return kOk;") < body.index("hipStream_t st = t_stream;")

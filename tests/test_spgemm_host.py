@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
-from test_coo_host import LONG_RUN, SHARED, _FakeTensor, _f, _i, coo_sum_model
+from test_coo_host import HELPERS, LONG_RUN, SHARED, _FakeTensor, _f, _i, coo_sum_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -65,9 +65,9 @@ SPGEMM_SIZE_RULES = [
      [GPU], "pa == pb == start == NULL: the map lives in the workspace (28 B instead of 16 B per product)"),
     ("map pass only when something reads it", CSRC + "spgemm.cpp", r"if \(d_pa \|\| d_c_value\) launch_spgemm_map\(",
      [GPU], "structure only and no map: the sorted order is dropped unread"),
-    ("kSpgemmAlign", CSRC + "spgemm.cpp", r"constexpr size_t kSpgemmAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      [GPU], "workspace parts are padded to 256 B (counts that are no multiple of 64: most cases)"),
-    ("int32 block arithmetic", CSRC + "spgemm.cpp", r"bool spgemm_too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      ["test_spgemm_contract"], "m, k, n, nnz_a, nnz_b or the product count beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
     ("key bits from m and n", CSRC + "spgemm.cpp", r"key_bits = coo_index_bits\(m\) \+ col_bits;",
      [GPU], "radix-sort passes follow the shape of C: 1 x 1 sorts 2 bits, 70 000 x 70 000 sorts 34 (more than 32), 200 000 x 100 000 sorts 35"),

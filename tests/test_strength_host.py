@@ -316,7 +316,7 @@ def test_strength_entries_keep_no_state():
     values = code.split("int run_csr_strength_values")[1]
     assert "hipMalloc" not in values and "Synchronize" not in values and "hipMemcpy" not in values and "hipMemset" not in values  # launch-only
     assert "plan_work_allowed" not in values and values.count("launch_strength_diag(") == 1 and values.count("launch_strength_values(") == 1
-    assert values.index("launch_strength_diag(") < values.index("launch_strength_values(") and len(re.findall(r"\blaunch_\w+\(", values)) == 2
+    assert re.findall(r"\blaunch_\w+\(", values) == ["launch_strength_diag(", "launch_strength_values(", "launch_error("]  # two kernels, then the check
     assert values.index("overlaps an output") < values.index("diag overlaps value") < values.index("launch_strength_diag(")  # refused before any launch
     assert values.index("omega must be finite") < values.index("launch_strength_diag(")
     kernels = open(os.path.join(ROOT, CSRC, "k_strength.hip")).read()

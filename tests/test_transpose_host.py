@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import spmv_acc_amd
+from test_coo_host import HELPERS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "spmv_acc_amd/csrc/"
@@ -36,11 +37,11 @@ TRANSPOSE_SIZE_RULES = [
     ("sort size paths", CSRC + "k_transpose.hip", r"rocprim::radix_sort_pairs\(tmp, \*tmp_bytes, ci, keys_out, rocprim::counting_iterator<int>\(0\), perm,",
      ["test_transpose_is_the_host_stable_argsort"],
      "the library sort picks its algorithm by size: matrices of 2 049 ... 3.2 M non-zeros cross its single-block, merge and multi-pass forms"),
-    ("int32 block arithmetic", CSRC + "transpose.cpp", r"bool too_large\(int v\) \{ return v > INT_MAX - \(1 << 16\); \}",
+    ("int32 block arithmetic", CSRC + HELPERS, r"inline bool too_large\(long long v\) \{ return v > INT_MAX - \(1 << 16\); \}",
      ["test_spmv_t_contract"], "m, n or nnz beyond this: SPMV_ACC_ERR_TOO_LARGE, as the other entries"),
     ("workspace with / without perm", CSRC + "transpose.cpp", r"off_bad = off_perm \+ \(d_perm \? 0 : ints\)",
      ["test_transpose_is_the_host_stable_argsort"], "perm == NULL: the permutation lives in the workspace (12 B instead of 8 B per non-zero)"),
-    ("kTransAlign", CSRC + "transpose.cpp", r"constexpr size_t kTransAlign = 256;",
+    ("kEntryAlign", CSRC + HELPERS, r"constexpr size_t kEntryAlign = 256;",
      ["test_transpose_is_the_host_stable_argsort"], "workspace parts are padded to 256 B (nnz not a multiple of 64 ints: the hub matrices)"),
 ]
 
