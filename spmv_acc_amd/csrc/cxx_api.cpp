@@ -89,7 +89,12 @@ void adaptive_vec_row_sparse_spmv(const int nnz_block_0, const int nnz_block_1, 
                                   double *y) {
   // the caller already knows the halves' nnz: build the samples the split needs without touching rowptr
   const int m = d_csr_desc.rows;
-  if (m <= 0) return;
+  // no plan and no engine call here, so the engine's word on the arguments is asked for directly: trans is reported, not applied
+  if (!spmv_call_accepted(trans, m, d_csr_desc.cols, d_csr_desc.row_ptr, x, y)) return;
+  if (d_csr_desc.nnz > 0 && (!d_csr_desc.col_index || !d_csr_desc.values)) {
+    set_error(kErrBadArgument, "null colindex / value with nnz > 0");
+    return;
+  }
   CsrDev A;
   A.m = m;
   A.n = d_csr_desc.cols;
@@ -107,7 +112,6 @@ void adaptive_vec_row_sparse_spmv(const int nnz_block_0, const int nnz_block_1, 
   const int half = m / 2;
   const int w0 = vec_for(half > 0 ? nnz_block_0 / half : 0);
   const int w1 = vec_for(nnz_block_1 / (m - half));
-  (void)trans;
   // the two-width split on the tile machinery (k_vector_row.hip::vector_tile_kernel); no plan is involved: the caller passed
   // the only structural facts the split needs
   const double a0 = half > 0 ? static_cast<double>(nnz_block_0) / half : 0.0;

@@ -775,6 +775,22 @@ static int slab_copy_auto(Plan &p, int strategy, hipStream_t st, int n, const do
   return S;
 }
 
+// run_spmv_call's answers about a call's arguments (below: the same codes and words, in the same order), for the one entry that launches without
+// the engine, adaptive_vec_row_sparse_spmv
+bool spmv_call_accepted(int trans, int m, int n, const int *d_rowptr, const double *dx, const double *dy) {
+  if (trans != 0) set_error(kErrUnsupportedTrans, "only operation_none is supported; computed y = alpha*A*x + beta*y");
+  if (m <= 0) return false;
+  if (m > INT_MAX - (1 << 16)) {
+    set_error(kErrTooLarge, "row count does not leave room for block arithmetic in int32; shard the matrix");
+    return false;
+  }
+  if (!d_rowptr || !dy || (n > 0 && !dx)) {
+    set_error(kErrBadArgument, "null rowptr / x / y");
+    return false;
+  }
+  return true;
+}
+
 namespace {
 thread_local bool t_early_clock = false; // run_spmv's rule-twin path: the tuning pass's budget clock started when the CALL began (twin's serve included)
 thread_local std::chrono::steady_clock::time_point t_early_began;
@@ -1116,8 +1132,10 @@ void run_spmv_call(int strategy, int trans, double alpha, double beta, int m, in
           const double f1 = (static_cast<double>(p->samples.last) - p->samples.half) / (m - half_rows);
           launch_vector_tile(st, p->A, half_rows, tile_vec(a0), tile_vec(a1), f0, f1, kVectorTarget,
                              tun(kT_xcd_chunk), policy_for(*p, kFamVector), alpha, beta, dx, dy);
+          p->last_kernel = kKernelVectorTile;
         } else {
           launch_vector_row(st, p->A, half_rows, classic_vec(a0), classic_vec(a1), alpha, beta, dx, dy);
+          p->last_kernel = kKernelVectorRow;
         }
       } else {
         run_plus(st, *p, h_rowptr, alpha, beta, dx, dy);

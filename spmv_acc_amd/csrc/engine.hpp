@@ -115,6 +115,11 @@ int plus_pick_vec_tuned(int m, int nnz, int min_nnz); // row cap chosen so block
 void run_spmv(int strategy, int trans, double alpha, double beta, int m, int n, int nnz, const int *h_rowptr,
               const int *d_rowptr, const int *d_colindex, const double *d_value, const double *dx, double *dy,
               const double *dy_in = nullptr);
+// What run_spmv says about a call's arguments before it touches the device, for adaptive_vec_row_sparse_spmv, which launches without the
+// engine: trans != 0 is reported (kErrUnsupportedTrans; the non-transposed product is still computed), a row count without room for int32
+// block arithmetic is kErrTooLarge, a null rowptr / y, or a null x with n > 0, is kErrBadArgument.  Returns false when there is nothing to
+// launch: one of the two refusals, or m <= 0.
+bool spmv_call_accepted(int trans, int m, int n, const int *d_rowptr, const double *dx, const double *dy);
 
 // One SpMM Y = alpha*A*X + beta*Y for k vectors (spmm.cpp; include/spmv_acc.h spmv_acc_csr_spmm): layout 0 row-major, 1 column-major.
 // Returns kOk or the error code it also leaves in the calling thread's error slot.
